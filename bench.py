@@ -7,6 +7,12 @@ N x N fp64 matrix (the reference miniapp's repetition unit,
 examples/conflux_miniapp.cpp:138-167).
 
     python bench.py [--gpus N] [--steps K] [--warmup W]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR then also writes what the last timed step returned to its
+caller as DIR/<name>.npy (see dump_outputs).  --full adds the legs that take
+runs of their own: today the CPU baseline of the compiled reference.
 
 Single process when N==1; for N>1 the driver launches this file under
 torch.distributed.run with one rank per GPU — torch.distributed (gloo) is
@@ -69,7 +75,7 @@ def cpu_baseline():
             ["/opt/conda/bin/mpiexec", "-n", str(n_ranks), ref, str(N),
              str(v), grid[0], grid[1], grid[2], "-", "/tmp/confluxref_bench",
              "2"],
-            env=env, capture_output=True, text=True, timeout=900)
+            env=env, capture_output=True, text=True, timeout=420)
         ms = None
         for line in out.stdout.splitlines():
             if line.startswith("_result_"):
@@ -86,6 +92,21 @@ def cpu_baseline():
         return None
 
 
+def dump_outputs(eng, outdir):
+    """Write the arrays the timed path hands back to its caller after the
+    last timed step.  The timed path runs with factor collection off (the
+    reference's non-VALIDATION build), so what a caller receives is the
+    global pivot vector: perm[r] = the row of A that became row r of PA,
+    identical on every rank.  Stored as float64 (N <= 2^53 is exact) in
+    perm.npy; 8N bytes, 0.5 MB at the largest bench size.  The input is the
+    seeded device-side generator, so the same arguments give the same
+    matrix on every run."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "perm.npy"),
+            eng.get_perm().astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None)
@@ -95,7 +116,16 @@ def main():
     ap.add_argument("--tile", "--v", dest="v", type=int, default=None,
                     help="override tile size")
     ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure "
+                         "(CPU baseline of the compiled reference)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -209,6 +239,9 @@ def main():
             "traffic": traffic,
         }
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
+
     eng.close()
 
     if rank == 0:
@@ -238,7 +271,7 @@ def main():
         }
         if roofline:
             result["roofline"] = roofline
-        if n_gpus == 1 and not args.skip_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.skip_cpu_baseline:
             cb = cpu_baseline()
             if cb:
                 result["cpu_baseline"] = cb

@@ -22,6 +22,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.join(HERE, "..")
 SHIM = os.path.join(HERE, "shimccl.so")
 MINIAPP = os.path.join(REPO, "conflux_amd", "conflux_miniapp")
+MAX_RANK_PROCS = 8  # worker processes per distributed run
 
 pytestmark = pytest.mark.gpu
 
@@ -44,15 +45,21 @@ def _run_ranks(tmp_path, N, v, Px, Py, Pz, reps=1, timeout=600,
         pytest.skip("shimccl.so not built (make -C tests)")
     P = Px * Py * Pz
     env = _dist_env(tmp_path, async_mode)
-    procs, outs = [], []
-    for r in range(P):
-        out = str(tmp_path / f"rank{r}.npz")
-        outs.append(out)
+    outs = [str(tmp_path / f"rank{r}.npz") for r in range(P)]
+    # one process per rank up to MAX_RANK_PROCS; a larger world packs
+    # consecutive ranks into one process, one host thread each (see
+    # dist_worker.py), so that this process and the workers together stay
+    # within the number of processes that may hold one device open
+    per = -(-P // MAX_RANK_PROCS)
+    procs = []
+    for r0 in range(0, P, per):
+        rs = range(r0, min(r0 + per, P))
         procs.append(subprocess.Popen(
             [sys.executable, os.path.join(HERE, "dist_worker.py"),
-             str(N), str(v), str(Px), str(Py), str(Pz), str(r), str(reps),
-             out] + (["set_matrix"] if set_matrix else [mode] if mode
-                     else []),
+             str(N), str(v), str(Px), str(Py), str(Pz),
+             ",".join(str(r) for r in rs), str(reps),
+             ",".join(outs[r] for r in rs)]
+            + (["set_matrix"] if set_matrix else [mode] if mode else []),
             env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
             text=True))
     logs = []
@@ -64,8 +71,9 @@ def _run_ranks(tmp_path, N, v, Px, Py, Pz, reps=1, timeout=600,
         for p in procs:
             if p.poll() is None:
                 p.kill()
-    for r, (p, log) in enumerate(zip(procs, logs)):
-        assert p.returncode == 0, f"rank {r} failed:\n{log}"
+    for i, (p, log) in enumerate(zip(procs, logs)):
+        assert p.returncode == 0, \
+            f"ranks {i * per}..{min((i + 1) * per, P) - 1} failed:\n{log}"
     return [np.load(o) for o in outs]
 
 
