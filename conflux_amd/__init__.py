@@ -65,6 +65,16 @@ def _load():
     lib.conflux_lu_debug_trsm.argtypes = [
         ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int,
         ctypes.c_void_p, ctypes.c_void_p]
+    lib.conflux_lu_solve.argtypes = [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+        ctypes.POINTER(ctypes.c_double)]
+    lib.conflux_chol_solve.argtypes = lib.conflux_lu_solve.argtypes
+    lib.conflux_lu_debug_trsm_left.argtypes = [
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong,
+        ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p]
+    lib.conflux_lu_debug_update_skinny.argtypes = [
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     return lib
 
 
@@ -179,6 +189,34 @@ class Engine:
         _chk(lib().conflux_chol_validate(self._h, ctypes.byref(r)),
              "chol_validate")
         return r.value
+
+    def _solve(self, fn, what, B, return_ms):
+        import numpy as np
+        B = np.asarray(B)
+        if B.ndim not in (1, 2) or B.shape[0] != self.Npad:
+            raise ValueError(
+                f"{what}: B must be ({self.Npad},) or ({self.Npad}, nrhs), "
+                f"got {B.shape}")
+        X = np.array(B, dtype=np.float64, order="C")  # always a fresh copy
+        nrhs = 1 if X.ndim == 1 else X.shape[1]
+        ms = ctypes.c_double()
+        _chk(fn(self._h, X.ctypes.data_as(ctypes.c_void_p), nrhs,
+                ctypes.byref(ms)), what)
+        return (X, ms.value) if return_ms else X
+
+    def solve(self, B, return_ms=False):
+        """Solve A X = B with the stored factors of the last factor()
+        (store_factors on).  B: (Npad,) or (Npad, nrhs); returns a new array
+        of the same shape, B itself is untouched.  return_ms=True also
+        returns the device time of the two sweeps.  Single process only:
+        a world > 1 engine raises ConfluxLuError (rc = EARG)."""
+        return self._solve(lib().conflux_lu_solve, "solve", B, return_ms)
+
+    def solve_cholesky(self, B, return_ms=False):
+        """Solve L L^T X = B with the factor of the last factor_cholesky()
+        (same conventions as solve)."""
+        return self._solve(lib().conflux_chol_solve, "solve_cholesky", B,
+                           return_ms)
 
     def get_perm(self):
         import numpy as np

@@ -111,6 +111,8 @@ struct Ctx {
     bool sim = false;            // all ranks in this process, 1 GPU
     bool input_dirty = true;     // A11 holds fresh input not yet snapshotted
     bool store_factors = true;
+    int factored_kind = 0;       // stored factors a solve may use: 0 = none,
+                                 // 1 = LU, 2 = Cholesky
     int pivoting = 1;            // 1 = tournament (reference), 0 = none
                                  // (EmptyPivot fast path)
     bool have_comm = false;
@@ -2340,10 +2342,13 @@ static int snapshot_or_restore(conflux_lu_ctx *c);
  * triangle valid). */
 int conflux_chol_factor(conflux_lu_ctx *c, double *elapsed_ms) {
     if (snapshot_or_restore(c)) return CONFLUX_LU_EHIP;
+    c->factored_kind = 0;
     int rc = chol_loop(*c, elapsed_ms);
     if (rc)
         std::fprintf(stderr, "[conflux_lu] chol failed: %s\n",
                      c->err.c_str());
+    else if (c->store_factors)
+        c->factored_kind = 2;
     return rc;
 }
 
@@ -2432,11 +2437,14 @@ static int snapshot_or_restore(conflux_lu_ctx *c) {
 
 int conflux_lu_factor(conflux_lu_ctx *c, double *elapsed_ms) {
     if (snapshot_or_restore(c)) return CONFLUX_LU_EHIP;
+    c->factored_kind = 0;
     int rc = c->pivoting ? factor_loop(*c, elapsed_ms)
                          : nopiv_loop(*c, elapsed_ms);
     if (rc) {
         std::fprintf(stderr, "[conflux_lu] factor failed: %s\n",
                      c->err.c_str());
+    } else if (c->store_factors) {
+        c->factored_kind = 1;
     }
     return rc;
 }
@@ -2641,6 +2649,180 @@ int conflux_chol_validate(conflux_lu_ctx *c, double *resid) {
     return validate_common(c, true, resid);
 }
 
+/* Multi-RHS solve on the stored factors (getrs / potrs).  The reference has
+ * no solve; this consumes what LU_rep leaves behind — the C result buffer
+ * and perm (conflux_opt.hpp:1660-1754).
+ *
+ * Block right-looking, block size sb | v (solve_block), entirely on device:
+ *   X <- B[perm]                              (LU; Cholesky: X <- B)
+ *   forward,  k = 0 .. Nt-1:  X_k <- L_kk^-1 X_k;  X[k+1:] -= F[k+1:, k] X_k
+ *   backward, k = Nt-1 .. 0:  X_k <- U_kk^-1 X_k;  X[:k]   -= F[:k, k]   X_k
+ * Both updates are tall (rows x v)(v x nrhs) products — many row tiles, so
+ * the chip stays busy at nrhs = 1.
+ *
+ * F aliasing rule: Fres is never written.  Px = Py = 1 LU reads it in place
+ * (Fres IS global F, ld = Nl; no N^2 buffer, so bench-scale N still fits);
+ * every other case works on one N^2 staging copy assembled with
+ * validate_common's owner map.  Cholesky always stages: the stored upper
+ * half of L is junk, so L is mirrored up and the backward sweep (with L^T)
+ * becomes the LU code.
+ *
+ * Real distributed runs (world > 1 processes) are NOT YET SUPPORTED: EARG on
+ * every rank before any communication (a collective solve is a follow-up). */
+static bool solve_use_skinny() {  // env CONFLUX_SOLVE_SKINNY=0|1, read once
+    static int on = -1;
+    if (on < 0) {
+        const char *e = getenv("CONFLUX_SOLVE_SKINNY");
+        on = e ? (atoi(e) != 0) : 1;
+    }
+    return on != 0;
+}
+
+// Sweep block size.  A v x v triangle is ONE block walking v/32 dependent
+// panels, while the update spreads over the whole chip, so a block smaller
+// than the factorization tile moves work from the serial kernel into the
+// parallel one: at N=16384 v=512 a 128 block measured 21.8 / 30.1 ms
+// (nrhs 1 / 128) against 34.2 / 40.1 ms with the full tile (64 and 256 are
+// within 10% of 128, 32 loses at nrhs >= 128).  Default: 128 when it
+// divides a larger v, else v.  env CONFLUX_SOLVE_BLOCK (read once) overrides
+// when it divides v.
+static int solve_block(int v) {
+    static int want = -1;
+    if (want < 0) {
+        const char *e = getenv("CONFLUX_SOLVE_BLOCK");
+        want = e ? atoi(e) : 0;
+    }
+    if (want > 0 && want <= v && v % want == 0) return want;
+    return (v > 128 && v % 128 == 0) ? 128 : v;
+}
+
+static int solve_common(conflux_lu_ctx *c, bool chol, double *B, int nrhs,
+                        double *elapsed_ms) {
+    if (!c || !B || nrhs <= 0) return CONFLUX_LU_EARG;
+    if (c->factored_kind != (chol ? 2 : 1)) return CONFLUX_LU_EARG;
+    if (!c->sim && c->world > 1) return CONFLUX_LU_EARG;  // not yet supported
+    RankState *r00 = c->sim ? get_rs(*c, 0, 0, 0) : &c->rs[0];
+    if (!r00->Fres) return CONFLUX_LU_EARG;
+    const int64_t N = c->N;
+    const int v = c->v;
+    const int Nt = (int)(N / v);
+    const bool aliasF = !chol && c->Px == 1 && c->Py == 1;
+
+    double *Fg = nullptr, *Xd = nullptr, *Bd = nullptr;
+    int *d_pm = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto cleanup = [&]() {
+        if (Fg && !aliasF) (void)hipFree(Fg);
+        for (double *p : {Xd, Bd})
+            if (p) (void)hipFree(p);
+        if (d_pm) (void)hipFree(d_pm);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    };
+#define SCHK(x)                                                               \
+    if ((x) != hipSuccess) {                                                  \
+        cleanup();                                                            \
+        return CONFLUX_LU_EHIP;                                               \
+    }
+    int64_t ldf = N;
+    if (aliasF) {
+        Fg = r00->Fres;
+        ldf = c->Nl;
+    } else {
+        SCHK(hipMalloc(&Fg, N * N * 8));
+        // tile-cyclic locals -> global F (owner map layout.cpp:95-123; the
+        // pk == 0 layers hold the data)
+        for (int pi = 0; pi < c->Px; ++pi)
+            for (int pj = 0; pj < c->Py; ++pj) {
+                const RankState *r = c->sim ? get_rs(*c, pi, pj, 0) : r00;
+                if (!r->Fres) {
+                    cleanup();
+                    return CONFLUX_LU_EARG;
+                }
+                if (c->Px == 1 && c->Py == 1) {
+                    launch_copy2d(r->Fres, c->Nl, Fg, N, c->Ml, c->Nl,
+                                  c->stream);
+                    continue;
+                }
+                for (int ti = pi; ti < Nt; ti += c->Px)
+                    for (int tj = pj; tj < Nt; tj += c->Py)
+                        launch_copy2d(r->Fres + i64(ti / c->Px) * v * c->Nl +
+                                          i64(tj / c->Py) * v,
+                                      c->Nl, Fg + i64(ti) * v * N + tj * v, N,
+                                      v, v, c->stream);
+            }
+        if (chol) launch_transpose_add_lower(Fg, N, c->stream);
+    }
+    SCHK(hipMalloc(&Xd, N * nrhs * 8));
+    if (chol) {
+        SCHK(hipMemcpyAsync(Xd, B, N * nrhs * 8, hipMemcpyHostToDevice,
+                            c->stream));
+    } else {
+        // row r of PA is row perm[r] of A, so X <- B[perm]
+        SCHK(hipMalloc(&Bd, N * nrhs * 8));
+        SCHK(hipMalloc(&d_pm, N * 4));
+        SCHK(hipMemcpyAsync(Bd, B, N * nrhs * 8, hipMemcpyHostToDevice,
+                            c->stream));
+        SCHK(hipMemcpyAsync(d_pm, c->pivotInds.data(), N * 4,
+                            hipMemcpyHostToDevice, c->stream));
+        launch_row_gather(Bd, nrhs, Xd, nrhs, d_pm, (int)N, nrhs, c->stream);
+    }
+    SCHK(hipEventCreate(&e0));
+    SCHK(hipEventCreate(&e1));
+    SCHK(hipEventRecord(e0, c->stream));
+
+    const bool skinny = nrhs <= 16 && solve_use_skinny();
+    const int sb = solve_block(v);  // sweep block size, divides v
+    const int nb = (int)(N / sb);
+    auto update = [&](const double *A, const double *Xk, double *C, int M) {
+        if (M <= 0) return;
+        if (skinny)
+            launch_update_skinny(A, ldf, Xk, nrhs, C, nrhs, M, nrhs, sb,
+                                 c->stream);
+        else
+            launch_dgemm_f64(A, ldf, Xk, nrhs, C, nrhs, M, nrhs, sb,
+                             c->stream);
+    };
+    for (int k = 0; k < nb; ++k) {  // forward: L (unit for LU)
+        const int64_t o = i64(k) * sb;
+        double *Xk = Xd + o * nrhs;
+        launch_trsm_left_tri_mfma(Fg + o * ldf + o, ldf, Xk, nrhs, sb, nrhs, 0,
+                                  chol ? 0 : 1, c->stream);
+        update(Fg + (o + sb) * ldf + o, Xk, Xk + i64(sb) * nrhs,
+               (int)(N - o - sb));
+    }
+    for (int k = nb - 1; k >= 0; --k) {  // backward: U (or L^T, mirrored up)
+        const int64_t o = i64(k) * sb;
+        double *Xk = Xd + o * nrhs;
+        launch_trsm_left_tri_mfma(Fg + o * ldf + o, ldf, Xk, nrhs, sb, nrhs, 1,
+                                  0, c->stream);
+        update(Fg + o, Xk, Xd, (int)o);
+    }
+    SCHK(hipEventRecord(e1, c->stream));
+    SCHK(hipMemcpyAsync(B, Xd, N * nrhs * 8, hipMemcpyDeviceToHost,
+                        c->stream));
+    SCHK(hipStreamSynchronize(c->stream));
+    SCHK(hipGetLastError());
+    if (elapsed_ms) {
+        float ms = 0;
+        SCHK(hipEventElapsedTime(&ms, e0, e1));
+        *elapsed_ms = ms;
+    }
+#undef SCHK
+    cleanup();
+    return CONFLUX_LU_OK;
+}
+
+int conflux_lu_solve(conflux_lu_ctx *c, double *B, int nrhs,
+                     double *elapsed_ms) {
+    return solve_common(c, false, B, nrhs, elapsed_ms);
+}
+
+int conflux_chol_solve(conflux_lu_ctx *c, double *B, int nrhs,
+                       double *elapsed_ms) {
+    return solve_common(c, true, B, nrhs, elapsed_ms);
+}
+
 int conflux_lu_get_factors(conflux_lu_ctx *c, double *F_local, int *perm) {
     if (c->sim) return conflux_lu_get_factors_sim(c, 0, F_local, perm);
     RankState &r = c->rs[0];
@@ -2838,6 +3020,66 @@ int conflux_lu_debug_trsm(int side_right, int M_or_v, int64_t N_or_M,
     (void)hipStreamDestroy(c.stream);
     (void)M_or_v;
     return rc;
+}
+
+// X (v x N) <- T^-1 X with T (v x ldt host, only its triangle read)
+int conflux_lu_debug_trsm_left(int upper, int unit, int v, int64_t N,
+                               int64_t ldt, const double *T, double *X) {
+    if (v <= 0 || N <= 0 || ldt < v || !T || !X) return CONFLUX_LU_EARG;
+    double *dT = nullptr, *dX = nullptr;
+    auto cleanup = [&]() {
+        for (double *p : {dT, dX})
+            if (p) (void)hipFree(p);
+    };
+    hipError_t e = hipMalloc(&dT, i64(v) * ldt * 8);
+    if (e == hipSuccess) e = hipMalloc(&dX, i64(v) * N * 8);
+    if (e == hipSuccess)
+        e = hipMemcpy(dT, T, i64(v) * ldt * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMemcpy(dX, X, i64(v) * N * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_trsm_left_tri_mfma(dT, ldt, dX, N, v, N, upper, unit, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess)
+        e = hipMemcpy(X, dX, i64(v) * N * 8, hipMemcpyDeviceToHost);
+    cleanup();
+    HIPCHK(e);
+    return CONFLUX_LU_OK;
+}
+
+// C (M x nrhs) -= A (M x lda host, K columns used) * B (K x nrhs)
+int conflux_lu_debug_update_skinny(int M, int nrhs, int K, int64_t lda,
+                                   const double *A, const double *B,
+                                   double *C) {
+    if (M <= 0 || nrhs <= 0 || nrhs > 16 || K <= 0 || lda < K || !A || !B ||
+        !C)
+        return CONFLUX_LU_EARG;
+    double *dA = nullptr, *dB = nullptr, *dC = nullptr;
+    auto cleanup = [&]() {
+        for (double *p : {dA, dB, dC})
+            if (p) (void)hipFree(p);
+    };
+    hipError_t e = hipMalloc(&dA, i64(M) * lda * 8);
+    if (e == hipSuccess) e = hipMalloc(&dB, i64(K) * nrhs * 8);
+    if (e == hipSuccess) e = hipMalloc(&dC, i64(M) * nrhs * 8);
+    if (e == hipSuccess)
+        e = hipMemcpy(dA, A, i64(M) * lda * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMemcpy(dB, B, i64(K) * nrhs * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMemcpy(dC, C, i64(M) * nrhs * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_update_skinny(dA, lda, dB, nrhs, dC, nrhs, M, nrhs, K, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess)
+        e = hipMemcpy(C, dC, i64(M) * nrhs * 8, hipMemcpyDeviceToHost);
+    cleanup();
+    HIPCHK(e);
+    return CONFLUX_LU_OK;
 }
 
 int conflux_lu_destroy(conflux_lu_ctx *c) {

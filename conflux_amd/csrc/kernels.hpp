@@ -45,6 +45,14 @@ void launch_trsm_right_mfma(const double *U, int64_t ldu, double *X,
                             hipStream_t s);
 void launch_trsm_left_mfma(const double *L, int64_t ldl, double *X,
                            int64_t ldx, int v, int64_t N, hipStream_t s);
+// solve_kernels.hip: X (v x N) <- T^-1 X, T lower/upper, unit/non-unit, any
+// v >= 1, read in place (ldt = the global N); C (M x nrhs) -= A B, nrhs <= 16
+void launch_trsm_left_tri_mfma(const double *T, int64_t ldt, double *X,
+                               int64_t ldx, int v, int64_t N, int upper,
+                               int unit, hipStream_t s);
+void launch_update_skinny(const double *A, int64_t lda, const double *B,
+                          int64_t ldb, double *C, int64_t ldc, int M, int nrhs,
+                          int K, hipStream_t s);
 void launch_tril_unit(const double *F, double *L, int64_t n, hipStream_t s);
 void launch_tril_unit_rows(const double *F, int64_t ldf, double *L,
                            int64_t ldl, int rows, int64_t row0, int64_t ncols,
