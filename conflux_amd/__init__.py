@@ -75,6 +75,19 @@ def _load():
     lib.conflux_lu_debug_update_skinny.argtypes = [
         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.conflux_lu_solve_refined.argtypes = [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
+        ctypes.POINTER(ctypes.c_double)]
+    lib.conflux_chol_solve_refined.argtypes = \
+        lib.conflux_lu_solve_refined.argtypes
+    lib.conflux_lu_debug_residual_dd.argtypes = [
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.conflux_lu_debug_residual_group_width.argtypes = []
+    lib.conflux_lu_debug_residual_dd_bench.argtypes = [
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
     return lib
 
 
@@ -217,6 +230,49 @@ class Engine:
         (same conventions as solve)."""
         return self._solve(lib().conflux_chol_solve, "solve_cholesky", B,
                            return_ms)
+
+    def _solve_refined(self, fn, what, B, max_iter, return_info):
+        import numpy as np
+        B = np.asarray(B)
+        if B.ndim not in (1, 2) or B.shape[0] != self.Npad:
+            raise ValueError(
+                f"{what}: B must be ({self.Npad},) or ({self.Npad}, nrhs), "
+                f"got {B.shape}")
+        X = np.array(B, dtype=np.float64, order="C")  # always a fresh copy
+        nrhs = 1 if X.ndim == 1 else X.shape[1]
+        berr = np.zeros(nrhs)
+        ferr = np.zeros(nrhs)
+        iters = ctypes.c_int()
+        ms = ctypes.c_double()
+        _chk(fn(self._h, X.ctypes.data_as(ctypes.c_void_p), nrhs,
+                int(max_iter), berr.ctypes.data_as(ctypes.c_void_p),
+                ferr.ctypes.data_as(ctypes.c_void_p), ctypes.byref(iters),
+                ctypes.byref(ms)), what)
+        if not return_info:
+            return X
+        return X, dict(berr=berr, ferr=ferr, iters=iters.value, ms=ms.value)
+
+    def solve_refined(self, B, max_iter=10, return_info=False):
+        """solve() followed by up to max_iter passes of iterative refinement
+        with a doubled-precision residual (conflux_lu_solve_refined): makes
+        the no-pivot fast path backward stable on general input and recovers
+        the digits an ill-conditioned system loses.  Same conventions as
+        solve (B: (Npad,) or (Npad, nrhs), new array returned, B untouched);
+        max_iter=0 is the plain solve plus its backward error.
+        return_info=True returns (X, info), info = dict(berr=ndarray[nrhs]
+        backward error of the returned X, ferr=ndarray[nrhs] last relative
+        correction applied (an estimate, not a bound), iters=passes that
+        applied a correction, ms=device time)."""
+        return self._solve_refined(lib().conflux_lu_solve_refined,
+                                   "solve_refined", B, max_iter, return_info)
+
+    def solve_cholesky_refined(self, B, max_iter=10, return_info=False):
+        """Refined solve on the factor of the last factor_cholesky() (same
+        conventions as solve_refined).  The residual multiplies by the stored
+        input as it stands: both of its triangles must hold A."""
+        return self._solve_refined(lib().conflux_chol_solve_refined,
+                                   "solve_cholesky_refined", B, max_iter,
+                                   return_info)
 
     def get_perm(self):
         import numpy as np

@@ -113,6 +113,8 @@ struct Ctx {
     bool store_factors = true;
     int factored_kind = 0;       // stored factors a solve may use: 0 = none,
                                  // 1 = LU, 2 = Cholesky
+    double anorm_inf = -1;       // ||A11in||inf for the refined solves; < 0 =
+                                 // not computed since the last factorization
     int pivoting = 1;            // 1 = tournament (reference), 0 = none
                                  // (EmptyPivot fast path)
     bool have_comm = false;
@@ -2432,6 +2434,7 @@ static int snapshot_or_restore(conflux_lu_ctx *c) {
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     c->input_dirty = false;
+    c->anorm_inf = -1;
     return CONFLUX_LU_OK;
 }
 
@@ -2696,81 +2699,107 @@ static int solve_block(int v) {
     return (v > 128 && v % 128 == 0) ? 128 : v;
 }
 
-static int solve_common(conflux_lu_ctx *c, bool chol, double *B, int nrhs,
-                        double *elapsed_ms) {
+// What every solve on one factorization shares, built once per call: global
+// F (Fres in place, or one staged N^2 copy) and, for LU, perm on device.
+// The refinement loop runs many permute-and-sweep rounds on one of these.
+struct SolveDev {
+    double *Fg = nullptr;
+    int64_t ldf = 0;
+    bool aliasF = false;
+    int *d_pm = nullptr;  // LU only
+    void release() {
+        if (Fg && !aliasF) (void)hipFree(Fg);
+        if (d_pm) (void)hipFree(d_pm);
+        Fg = nullptr;
+        d_pm = nullptr;
+    }
+};
+
+// Tile-cyclic locals -> one global N x N buffer (owner map layout.cpp:95-123;
+// the pk == 0 layers hold the data).  `which` picks the local buffer.
+extern "C++" template <typename Pick>
+static int assemble_global(conflux_lu_ctx *c, double *G, Pick which) {
+    const int64_t N = c->N;
+    const int v = c->v;
+    const int Nt = (int)(N / v);
+    RankState *r00 = c->sim ? get_rs(*c, 0, 0, 0) : &c->rs[0];
+    for (int pi = 0; pi < c->Px; ++pi)
+        for (int pj = 0; pj < c->Py; ++pj) {
+            const RankState *r = c->sim ? get_rs(*c, pi, pj, 0) : r00;
+            const double *loc = which(*r);
+            if (!loc) return CONFLUX_LU_EARG;
+            if (c->Px == 1 && c->Py == 1) {
+                launch_copy2d(loc, c->Nl, G, N, c->Ml, c->Nl, c->stream);
+                continue;
+            }
+            for (int ti = pi; ti < Nt; ti += c->Px)
+                for (int tj = pj; tj < Nt; tj += c->Py)
+                    launch_copy2d(loc + i64(ti / c->Px) * v * c->Nl +
+                                      i64(tj / c->Py) * v,
+                                  c->Nl, G + i64(ti) * v * N + tj * v, N, v,
+                                  v, c->stream);
+        }
+    return CONFLUX_LU_OK;
+}
+
+// The guards every solve entry point shares.
+static int solve_guard(conflux_lu_ctx *c, bool chol, const double *B,
+                       int nrhs) {
     if (!c || !B || nrhs <= 0) return CONFLUX_LU_EARG;
     if (c->factored_kind != (chol ? 2 : 1)) return CONFLUX_LU_EARG;
     if (!c->sim && c->world > 1) return CONFLUX_LU_EARG;  // not yet supported
     RankState *r00 = c->sim ? get_rs(*c, 0, 0, 0) : &c->rs[0];
     if (!r00->Fres) return CONFLUX_LU_EARG;
+    return CONFLUX_LU_OK;
+}
+
+static int solve_stage(conflux_lu_ctx *c, bool chol, SolveDev &sd) {
+    const int64_t N = c->N;
+    RankState *r00 = c->sim ? get_rs(*c, 0, 0, 0) : &c->rs[0];
+    sd.aliasF = !chol && c->Px == 1 && c->Py == 1;
+    if (sd.aliasF) {
+        sd.Fg = r00->Fres;
+        sd.ldf = c->Nl;
+    } else {
+        sd.ldf = N;
+        if (hipMalloc(&sd.Fg, N * N * 8) != hipSuccess) return CONFLUX_LU_EHIP;
+        if (int rc = assemble_global(
+                c, sd.Fg, [](const RankState &r) { return r.Fres; }))
+            return rc;
+        if (chol) launch_transpose_add_lower(sd.Fg, N, c->stream);
+    }
+    if (!chol) {
+        if (hipMalloc(&sd.d_pm, N * 4) != hipSuccess) return CONFLUX_LU_EHIP;
+        if (hipMemcpyAsync(sd.d_pm, c->pivotInds.data(), N * 4,
+                           hipMemcpyHostToDevice, c->stream) != hipSuccess)
+            return CONFLUX_LU_EHIP;
+    }
+    return CONFLUX_LU_OK;
+}
+
+// Xd <- the right-hand side in the factors' row order: row r of PA is row
+// perm[r] of A, so X <- B[perm] (LU); Cholesky copies (or works in place
+// when Bd == Xd).  LU needs Bd != Xd.
+static int solve_permute(conflux_lu_ctx *c, bool chol, const SolveDev &sd,
+                         const double *Bd, double *Xd, int nrhs) {
+    const int64_t N = c->N;
+    if (!chol)
+        launch_row_gather(Bd, nrhs, Xd, nrhs, sd.d_pm, (int)N, nrhs,
+                          c->stream);
+    else if (Bd != Xd &&
+             hipMemcpyAsync(Xd, Bd, N * nrhs * 8, hipMemcpyDeviceToDevice,
+                            c->stream) != hipSuccess)
+        return CONFLUX_LU_EHIP;
+    return CONFLUX_LU_OK;
+}
+
+// The two sweeps, in place on the device buffer Xd (N x nrhs, ld = nrhs).
+static void solve_sweeps(conflux_lu_ctx *c, bool chol, const SolveDev &sd,
+                         double *Xd, int nrhs) {
     const int64_t N = c->N;
     const int v = c->v;
-    const int Nt = (int)(N / v);
-    const bool aliasF = !chol && c->Px == 1 && c->Py == 1;
-
-    double *Fg = nullptr, *Xd = nullptr, *Bd = nullptr;
-    int *d_pm = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&]() {
-        if (Fg && !aliasF) (void)hipFree(Fg);
-        for (double *p : {Xd, Bd})
-            if (p) (void)hipFree(p);
-        if (d_pm) (void)hipFree(d_pm);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    };
-#define SCHK(x)                                                               \
-    if ((x) != hipSuccess) {                                                  \
-        cleanup();                                                            \
-        return CONFLUX_LU_EHIP;                                               \
-    }
-    int64_t ldf = N;
-    if (aliasF) {
-        Fg = r00->Fres;
-        ldf = c->Nl;
-    } else {
-        SCHK(hipMalloc(&Fg, N * N * 8));
-        // tile-cyclic locals -> global F (owner map layout.cpp:95-123; the
-        // pk == 0 layers hold the data)
-        for (int pi = 0; pi < c->Px; ++pi)
-            for (int pj = 0; pj < c->Py; ++pj) {
-                const RankState *r = c->sim ? get_rs(*c, pi, pj, 0) : r00;
-                if (!r->Fres) {
-                    cleanup();
-                    return CONFLUX_LU_EARG;
-                }
-                if (c->Px == 1 && c->Py == 1) {
-                    launch_copy2d(r->Fres, c->Nl, Fg, N, c->Ml, c->Nl,
-                                  c->stream);
-                    continue;
-                }
-                for (int ti = pi; ti < Nt; ti += c->Px)
-                    for (int tj = pj; tj < Nt; tj += c->Py)
-                        launch_copy2d(r->Fres + i64(ti / c->Px) * v * c->Nl +
-                                          i64(tj / c->Py) * v,
-                                      c->Nl, Fg + i64(ti) * v * N + tj * v, N,
-                                      v, v, c->stream);
-            }
-        if (chol) launch_transpose_add_lower(Fg, N, c->stream);
-    }
-    SCHK(hipMalloc(&Xd, N * nrhs * 8));
-    if (chol) {
-        SCHK(hipMemcpyAsync(Xd, B, N * nrhs * 8, hipMemcpyHostToDevice,
-                            c->stream));
-    } else {
-        // row r of PA is row perm[r] of A, so X <- B[perm]
-        SCHK(hipMalloc(&Bd, N * nrhs * 8));
-        SCHK(hipMalloc(&d_pm, N * 4));
-        SCHK(hipMemcpyAsync(Bd, B, N * nrhs * 8, hipMemcpyHostToDevice,
-                            c->stream));
-        SCHK(hipMemcpyAsync(d_pm, c->pivotInds.data(), N * 4,
-                            hipMemcpyHostToDevice, c->stream));
-        launch_row_gather(Bd, nrhs, Xd, nrhs, d_pm, (int)N, nrhs, c->stream);
-    }
-    SCHK(hipEventCreate(&e0));
-    SCHK(hipEventCreate(&e1));
-    SCHK(hipEventRecord(e0, c->stream));
-
+    const double *Fg = sd.Fg;
+    const int64_t ldf = sd.ldf;
     const bool skinny = nrhs <= 16 && solve_use_skinny();
     const int sb = solve_block(v);  // sweep block size, divides v
     const int nb = (int)(N / sb);
@@ -2798,6 +2827,49 @@ static int solve_common(conflux_lu_ctx *c, bool chol, double *B, int nrhs,
                                   0, c->stream);
         update(Fg + o, Xk, Xd, (int)o);
     }
+}
+
+static int solve_common(conflux_lu_ctx *c, bool chol, double *B, int nrhs,
+                        double *elapsed_ms) {
+    if (int rc = solve_guard(c, chol, B, nrhs)) return rc;
+    const int64_t N = c->N;
+
+    SolveDev sd;
+    double *Xd = nullptr, *Bd = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto cleanup = [&]() {
+        sd.release();
+        for (double *p : {Xd, Bd})
+            if (p) (void)hipFree(p);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    };
+#define SCHK(x)                                                               \
+    if ((x) != hipSuccess) {                                                  \
+        cleanup();                                                            \
+        return CONFLUX_LU_EHIP;                                               \
+    }
+    if (int rc = solve_stage(c, chol, sd)) {
+        cleanup();
+        return rc;
+    }
+    SCHK(hipMalloc(&Xd, N * nrhs * 8));
+    if (chol) {
+        SCHK(hipMemcpyAsync(Xd, B, N * nrhs * 8, hipMemcpyHostToDevice,
+                            c->stream));
+    } else {
+        SCHK(hipMalloc(&Bd, N * nrhs * 8));
+        SCHK(hipMemcpyAsync(Bd, B, N * nrhs * 8, hipMemcpyHostToDevice,
+                            c->stream));
+    }
+    if (solve_permute(c, chol, sd, chol ? Xd : Bd, Xd, nrhs)) {
+        cleanup();
+        return CONFLUX_LU_EHIP;
+    }
+    SCHK(hipEventCreate(&e0));
+    SCHK(hipEventCreate(&e1));
+    SCHK(hipEventRecord(e0, c->stream));
+    solve_sweeps(c, chol, sd, Xd, nrhs);
     SCHK(hipEventRecord(e1, c->stream));
     SCHK(hipMemcpyAsync(B, Xd, N * nrhs * 8, hipMemcpyDeviceToHost,
                         c->stream));
@@ -2821,6 +2893,205 @@ int conflux_lu_solve(conflux_lu_ctx *c, double *B, int nrhs,
 int conflux_chol_solve(conflux_lu_ctx *c, double *B, int nrhs,
                        double *elapsed_ms) {
     return solve_common(c, true, B, nrhs, elapsed_ms);
+}
+
+/* Solve with extra-precise iterative refinement (the xGERFSX idea: the
+ * residual is accumulated in doubled precision and rounded once, so the
+ * correction solve sees the true residual even where B - A X cancels to
+ * nothing in working precision).  The reference has no counterpart.
+ *
+ *   X = solve(B);  it = 0
+ *   loop:
+ *     R = B - A X                      k_residual_dd on the stored input
+ *     berr_j = max|R_j| / (||A||inf max|X_j| + max|B_j|)
+ *     stop if it == max_iter or no column is active
+ *     D = solve(R)
+ *     per active column, d_j = max|D_j|:
+ *       it > 0 and d_j > d_prev_j / 2  -> stagnated: freeze, D_j NOT applied
+ *       else X_j += D_j, ferr_j = d_j / max|X_j|, and freeze as converged
+ *            when d_j <= 2^-53 max|X_j|
+ *     it += 1
+ * A column whose residual is exactly zero is frozen on the spot: there is
+ * nothing left to correct.  The decisions are taken on the host from the
+ * per-column maxima — nrhs doubles per download, two downloads and one
+ * nrhs-int mask upload per pass; X, R and D never leave the device.
+ *
+ * A is the input snapshot A11in, which the factorization never touches:
+ * read in place on a Px = Py = 1 grid (no N^2 buffer), else assembled into
+ * one N^2 staging copy with the owner map of the F staging.  ||A||inf is
+ * computed on first use and cached until the next factorization.  F and
+ * perm are staged once per call; every pass reuses them.
+ *
+ * Determinism: the residual kernel combines its partial accumulators in an
+ * order fixed by lane ids, the maxima are exact, so two calls agree
+ * bitwise. */
+static int solve_refined_common(conflux_lu_ctx *c, bool chol, double *B,
+                                int nrhs, int max_iter, double *berr,
+                                double *ferr, int *iters,
+                                double *elapsed_ms) {
+    if (int rc = solve_guard(c, chol, B, nrhs)) return rc;
+    if (max_iter < 0) return CONFLUX_LU_EARG;
+    const int64_t N = c->N;
+    RankState *r00 = c->sim ? get_rs(*c, 0, 0, 0) : &c->rs[0];
+    if (!r00->A11in) return CONFLUX_LU_EARG;
+    const bool aliasA = c->Px == 1 && c->Py == 1;
+
+    SolveDev sd;
+    double *Ag = nullptr, *Bd = nullptr, *Xd = nullptr, *Rd = nullptr,
+           *Dd = nullptr, *d_sc = nullptr, *d_rows = nullptr;
+    int *d_mask = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto cleanup = [&]() {
+        sd.release();
+        if (Ag && !aliasA) (void)hipFree(Ag);
+        if (Dd && Dd != Rd) (void)hipFree(Dd);
+        for (double *p : {Bd, Xd, Rd, d_sc, d_rows})
+            if (p) (void)hipFree(p);
+        if (d_mask) (void)hipFree(d_mask);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    };
+#define SCHK(x)                                                               \
+    if ((x) != hipSuccess) {                                                  \
+        cleanup();                                                            \
+        return CONFLUX_LU_EHIP;                                               \
+    }
+    if (int rc = solve_stage(c, chol, sd)) {
+        cleanup();
+        return rc;
+    }
+    int64_t lda = N;
+    if (aliasA) {
+        Ag = r00->A11in;
+        lda = c->Nl;
+    } else {
+        SCHK(hipMalloc(&Ag, N * N * 8));
+        if (int rc = assemble_global(
+                c, Ag, [](const RankState &r) { return r.A11in; })) {
+            cleanup();
+            return rc;
+        }
+    }
+    const size_t xb = (size_t)N * nrhs * 8;
+    SCHK(hipMalloc(&Bd, xb));
+    SCHK(hipMalloc(&Xd, xb));
+    SCHK(hipMalloc(&Rd, xb));
+    if (chol)
+        Dd = Rd;  // the Cholesky sweeps run in place on the residual
+    else
+        SCHK(hipMalloc(&Dd, xb));
+    SCHK(hipMalloc(&d_sc, (size_t)nrhs * 8));
+    SCHK(hipMalloc(&d_mask, (size_t)nrhs * 4));
+    SCHK(hipMemcpyAsync(Bd, B, xb, hipMemcpyHostToDevice, c->stream));
+
+    std::vector<double> xmax(nrhs), bmax(nrhs), rmax(nrhs), dmax(nrhs),
+        dprev(nrhs, 0.0), be(nrhs, 0.0), fe(nrhs, 0.0);
+    std::vector<int> active(nrhs, 1), mask(nrhs, 0);
+    // per-column max|.| of a device N x nrhs array -> host (synchronises)
+    auto colmax = [&](const double *V, std::vector<double> &out) {
+        launch_colmax_abs(V, N, nrhs, d_sc, c->stream);
+        hipError_t e = hipMemcpyAsync(out.data(), d_sc, (size_t)nrhs * 8,
+                                      hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        return e;
+    };
+    if (c->anorm_inf < 0) {  // once per factorization
+        SCHK(hipMalloc(&d_rows, (size_t)N * 8));
+        launch_row_abs_sums(Ag, lda, (int)N, (int)N, d_rows, c->stream);
+        launch_colmax_abs(d_rows, N, 1, d_sc, c->stream);
+        double nrm = 0;
+        SCHK(hipMemcpyAsync(&nrm, d_sc, 8, hipMemcpyDeviceToHost, c->stream));
+        SCHK(hipStreamSynchronize(c->stream));
+        c->anorm_inf = nrm;
+    }
+    const double anorm = c->anorm_inf;
+    SCHK(colmax(Bd, bmax));
+
+    SCHK(hipEventCreate(&e0));
+    SCHK(hipEventCreate(&e1));
+    SCHK(hipEventRecord(e0, c->stream));
+    if (solve_permute(c, chol, sd, Bd, Xd, nrhs)) {
+        cleanup();
+        return CONFLUX_LU_EHIP;
+    }
+    solve_sweeps(c, chol, sd, Xd, nrhs);
+    SCHK(colmax(Xd, xmax));
+
+    const double u = 0x1p-53;
+    int it = 0, applied_passes = 0;
+    for (;;) {
+        launch_residual_dd(Ag, lda, Xd, Bd, Rd, (int)N, (int)N, nrhs,
+                           c->stream);
+        SCHK(colmax(Rd, rmax));
+        int nactive = 0;
+        for (int j = 0; j < nrhs; ++j) {
+            const double den = anorm * xmax[j] + bmax[j];
+            be[j] = den == 0 ? 0.0 : rmax[j] / den;
+            if (rmax[j] == 0) active[j] = 0;  // exact: nothing to correct
+            nactive += active[j];
+        }
+        if (it == max_iter || nactive == 0) break;
+        if (solve_permute(c, chol, sd, Rd, Dd, nrhs)) {
+            cleanup();
+            return CONFLUX_LU_EHIP;
+        }
+        solve_sweeps(c, chol, sd, Dd, nrhs);
+        SCHK(colmax(Dd, dmax));
+        int napplied = 0;
+        for (int j = 0; j < nrhs; ++j) {
+            mask[j] = 0;
+            if (!active[j]) continue;
+            // !(d <= d_prev / 2) also catches a NaN correction
+            if (it > 0 && !(dmax[j] <= 0.5 * dprev[j])) {
+                active[j] = 0;  // stagnated: this correction is not applied
+                continue;
+            }
+            mask[j] = 1;
+            dprev[j] = dmax[j];
+            ++napplied;
+        }
+        ++it;
+        if (!napplied) break;  // X unchanged: berr above still describes it
+        SCHK(hipMemcpyAsync(d_mask, mask.data(), (size_t)nrhs * 4,
+                            hipMemcpyHostToDevice, c->stream));
+        launch_axpy_masked(Xd, Dd, d_mask, N, nrhs, c->stream);
+        SCHK(colmax(Xd, xmax));
+        for (int j = 0; j < nrhs; ++j) {
+            if (!mask[j]) continue;
+            fe[j] = xmax[j] == 0 ? 0.0 : dmax[j] / xmax[j];
+            if (dmax[j] <= u * xmax[j]) active[j] = 0;  // converged
+        }
+        ++applied_passes;
+    }
+    SCHK(hipEventRecord(e1, c->stream));
+    SCHK(hipMemcpyAsync(B, Xd, xb, hipMemcpyDeviceToHost, c->stream));
+    SCHK(hipStreamSynchronize(c->stream));
+    SCHK(hipGetLastError());
+    if (berr) std::copy(be.begin(), be.end(), berr);
+    if (ferr) std::copy(fe.begin(), fe.end(), ferr);
+    if (iters) *iters = applied_passes;
+    if (elapsed_ms) {
+        float ms = 0;
+        SCHK(hipEventElapsedTime(&ms, e0, e1));
+        *elapsed_ms = ms;
+    }
+#undef SCHK
+    cleanup();
+    return CONFLUX_LU_OK;
+}
+
+int conflux_lu_solve_refined(conflux_lu_ctx *c, double *B, int nrhs,
+                             int max_iter, double *berr, double *ferr,
+                             int *iters, double *elapsed_ms) {
+    return solve_refined_common(c, false, B, nrhs, max_iter, berr, ferr,
+                                iters, elapsed_ms);
+}
+
+int conflux_chol_solve_refined(conflux_lu_ctx *c, double *B, int nrhs,
+                               int max_iter, double *berr, double *ferr,
+                               int *iters, double *elapsed_ms) {
+    return solve_refined_common(c, true, B, nrhs, max_iter, berr, ferr, iters,
+                                elapsed_ms);
 }
 
 int conflux_lu_get_factors(conflux_lu_ctx *c, double *F_local, int *perm) {
@@ -3079,6 +3350,94 @@ int conflux_lu_debug_update_skinny(int M, int nrhs, int K, int64_t lda,
         e = hipMemcpy(C, dC, i64(M) * nrhs * 8, hipMemcpyDeviceToHost);
     cleanup();
     HIPCHK(e);
+    return CONFLUX_LU_OK;
+}
+
+// R (M x nrhs) = B - A (M x lda host, K columns used) * X (K x nrhs) with
+// the doubled-precision accumulator
+int conflux_lu_debug_residual_dd(int M, int K, int nrhs, int64_t lda,
+                                 const double *A, const double *X,
+                                 const double *B, double *R) {
+    if (M <= 0 || nrhs <= 0 || K <= 0 || lda < K || !A || !X || !B || !R)
+        return CONFLUX_LU_EARG;
+    double *dA = nullptr, *dX = nullptr, *dB = nullptr, *dR = nullptr;
+    auto cleanup = [&]() {
+        for (double *p : {dA, dX, dB, dR})
+            if (p) (void)hipFree(p);
+    };
+    hipError_t e = hipMalloc(&dA, i64(M) * lda * 8);
+    if (e == hipSuccess) e = hipMalloc(&dX, i64(K) * nrhs * 8);
+    if (e == hipSuccess) e = hipMalloc(&dB, i64(M) * nrhs * 8);
+    if (e == hipSuccess) e = hipMalloc(&dR, i64(M) * nrhs * 8);
+    if (e == hipSuccess)
+        e = hipMemcpy(dA, A, i64(M) * lda * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMemcpy(dX, X, i64(K) * nrhs * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMemcpy(dB, B, i64(M) * nrhs * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_residual_dd(dA, lda, dX, dB, dR, M, K, nrhs, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess)
+        e = hipMemcpy(R, dR, i64(M) * nrhs * 8, hipMemcpyDeviceToHost);
+    cleanup();
+    HIPCHK(e);
+    return CONFLUX_LU_OK;
+}
+
+int conflux_lu_debug_residual_group_width() {
+    return conflux_residual_group_width();
+}
+
+/* Device-only timing of the residual (tools/solve_bench.py --refine):
+ * ms_resid = mean ms of one R = B - A X over an M x K matrix and nrhs
+ * columns (ceil(nrhs / group width) passes over A); ms_copy = mean ms of a
+ * device-to-device copy of the same M*K*8 bytes, the bandwidth yardstick
+ * of the same run. */
+int conflux_lu_debug_residual_dd_bench(int M, int K, int nrhs, int iters,
+                                       double *ms_resid, double *ms_copy) {
+    if (M <= 0 || K <= 0 || nrhs <= 0 || iters <= 0 || !ms_resid || !ms_copy)
+        return CONFLUX_LU_EARG;
+    hipStream_t s;
+    HIPCHK(hipStreamCreate(&s));
+    double *dA, *dA2, *dX, *dB, *dR;
+    HIPCHK(hipMalloc(&dA, i64(M) * K * 8));
+    HIPCHK(hipMalloc(&dA2, i64(M) * K * 8));
+    HIPCHK(hipMalloc(&dX, i64(K) * nrhs * 8));
+    HIPCHK(hipMalloc(&dB, i64(M) * nrhs * 8));
+    HIPCHK(hipMalloc(&dR, i64(M) * nrhs * 8));
+    launch_init_matrix(dA, M, K, K, 1, 1, 0, 0, 0, 7, s);
+    launch_init_matrix(dX, K, nrhs, nrhs, 1, 1, 0, 0, 0, 8, s);
+    launch_init_matrix(dB, M, nrhs, nrhs, 1, 1, 0, 0, 0, 9, s);
+    hipEvent_t a, b;
+    HIPCHK(hipEventCreate(&a));
+    HIPCHK(hipEventCreate(&b));
+    float ms = 0;
+    launch_residual_dd(dA, K, dX, dB, dR, M, K, nrhs, s);  // warmup
+    HIPCHK(hipEventRecord(a, s));
+    for (int i = 0; i < iters; ++i)
+        launch_residual_dd(dA, K, dX, dB, dR, M, K, nrhs, s);
+    HIPCHK(hipEventRecord(b, s));
+    HIPCHK(hipEventSynchronize(b));
+    HIPCHK(hipEventElapsedTime(&ms, a, b));
+    *ms_resid = ms / iters;
+    HIPCHK(hipMemcpyAsync(dA2, dA, i64(M) * K * 8, hipMemcpyDeviceToDevice,
+                          s));  // warmup
+    HIPCHK(hipEventRecord(a, s));
+    for (int i = 0; i < iters; ++i)
+        HIPCHK(hipMemcpyAsync(dA2, dA, i64(M) * K * 8,
+                              hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipEventRecord(b, s));
+    HIPCHK(hipEventSynchronize(b));
+    HIPCHK(hipEventElapsedTime(&ms, a, b));
+    *ms_copy = ms / iters;
+    HIPCHK(hipGetLastError());
+    (void)hipFree(dA); (void)hipFree(dA2); (void)hipFree(dX);
+    (void)hipFree(dB); (void)hipFree(dR);
+    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
+    (void)hipStreamDestroy(s);
     return CONFLUX_LU_OK;
 }
 

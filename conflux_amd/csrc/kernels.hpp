@@ -53,6 +53,20 @@ void launch_trsm_left_tri_mfma(const double *T, int64_t ldt, double *X,
 void launch_update_skinny(const double *A, int64_t lda, const double *B,
                           int64_t ldb, double *C, int64_t ldc, int M, int nrhs,
                           int K, hipStream_t s);
+// solve_kernels.hip, refinement: R (M x nrhs) = B - A X in doubled precision
+// (ld of X, B, R = nrhs; R must not alias B or X), in passes of
+// conflux_residual_group_width() columns; out[row] = sum_k |A[row][k]|;
+// out[j] = max_i |V[i][j]|; X[:, j] += D[:, j] where mask[j] != 0
+void launch_residual_dd(const double *A, int64_t lda, const double *X,
+                        const double *B, double *R, int M, int K, int nrhs,
+                        hipStream_t s);
+int conflux_residual_group_width();
+void launch_row_abs_sums(const double *A, int64_t lda, int M, int K,
+                         double *out, hipStream_t s);
+void launch_colmax_abs(const double *V, int64_t n, int ncols, double *out,
+                       hipStream_t s);
+void launch_axpy_masked(double *X, const double *D, const int *mask,
+                        int64_t n, int ncols, hipStream_t s);
 void launch_tril_unit(const double *F, double *L, int64_t n, hipStream_t s);
 void launch_tril_unit_rows(const double *F, int64_t ldf, double *L,
                            int64_t ldl, int rows, int64_t row0, int64_t ncols,

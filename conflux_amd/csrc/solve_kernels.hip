@@ -10,13 +10,26 @@
 //                         the tall rank-v update of a sweep, bandwidth-bound
 //                         (each element of F is read once per sweep).
 //
-// Neither kernel synchronises across blocks: every block owns its slice of
-// X / C outright — no flags, no atomics, nothing that can spin.
+// and of the refined solves (conflux_lu_solve_refined /
+// conflux_chol_solve_refined), which the reference has no counterpart of
+// either:
+//
+//   k_residual_dd         R (M x nrhs) = B - A (M x K) X (K x nrhs) with a
+//                         doubled-precision accumulator (dd.hpp), one
+//                         rounding per entry; vector ALU, bandwidth-bound.
+//   k_row_abs_sums, k_colmax_abs, k_axpy_masked
+//                         ||A||inf, per-column max|.| and the masked X += D
+//                         of the refinement loop.
+//
+// No kernel synchronises across blocks: every block owns its slice of
+// X / C / R outright — no flags, no atomics, nothing that can spin — and
+// every reduction runs in a fixed order, so results are deterministic.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
 
+#include "dd.hpp"
 #include "kernels.hpp"
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
@@ -267,6 +280,181 @@ __global__ __launch_bounds__(256) void k_update_skinny(
     }
 }
 
+// ---------------------------------------------------------------------------
+// Extra-precise residual R (M x nrhs) = B - A (M x K) X (K x nrhs): every
+// product and every addition goes through the doubled accumulator of dd.hpp,
+// B enters as the accumulator's initial value, and each entry is rounded
+// exactly once, at the end.  MFMA cannot do this (it rounds per step), so
+// the work is on the vector ALU: 10 fp64 operations per (element of A,
+// column).
+//
+// Work split.  A wave owns RES_R = 4 rows outright and all of K; its 64
+// lanes walk ALONG k, lane l taking the 16-byte pair k = 128 * step + 2 l —
+// a wave reads 1 KiB contiguous per row and step (k_update_skinny's access
+// pattern, one row segment per wave instead of 16).  The block (4 waves,
+// 16 rows) stages X through LDS in RES_KC-deep chunks, column-major, so the
+// lanes' 16-byte LDS reads are contiguous and conflict-free and one X pair
+// is reused by the 4 rows.  M = 16384 gives 4096 waves, 4 per SIMD.  K is
+// NOT split across waves or blocks: the only cross-thread combination is
+// the 64-lane merge butterfly at the end of a row, whose order is fixed by
+// the lane ids, so R does not depend on the grid or on scheduling.
+//
+// Column group.  A launch handles NC <= RES_G = 4 columns in one pass over
+// A (a template parameter: the single-RHS pass must not pay for padding
+// columns); the launcher loops over groups.  4 rows x 4 columns of (s, c)
+// accumulators are 64 VGPRs, the double-buffered A pairs 32 and one X pair
+// 4.  The compiler's resource usage (-Rpass-analysis=kernel-resource-usage)
+// for NC = 1 / 2 / 3 / 4: 88 / 106 / 120 / 138 VGPRs, 5 / 4 / 4 / 3 waves
+// per SIMD, no VGPR or SGPR spill, no scratch.  8 columns would need 128
+// VGPRs for accumulators alone and halve the occupancy, to no gain: a pass
+// is already ALU-bound at 4 columns (10 * 4 operations per 8 bytes of A;
+// measured at 16384^2: 0.40 ms at NC = 1, the speed of the memory, 0.85 ms
+// at NC = 4).
+//
+// FAST: A 16-byte aligned and lda even, so every lane's pair is one 16-byte
+// load; otherwise (and for the last odd element of a row) scalar loads.
+// Elements at k >= K are never read: they enter as exact zeros.  Rows past
+// M re-read row M-1 (in bounds) and their results are dropped, so all four
+// waves reach every barrier.
+// ---------------------------------------------------------------------------
+#define RES_G 4
+#define RES_R 4
+#define RES_KC 1024
+template <int NC, bool FAST>
+__global__ __launch_bounds__(256) void k_residual_dd(
+    const double *__restrict__ A, int64_t lda, const double *__restrict__ X,
+    const double *__restrict__ B, double *__restrict__ R, int M, int K,
+    int nrhs, int c0) {
+    __shared__ double sX[NC][RES_KC];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int row0 = (blockIdx.x * 4 + wave) * RES_R;
+    const double *ap[RES_R];
+    dd::Acc acc[RES_R][NC];
+#pragma unroll
+    for (int r = 0; r < RES_R; ++r) {
+        const int row = min(row0 + r, M - 1);
+        ap[r] = A + (int64_t)row * lda;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            acc[r][c].s = lane == 0 ? B[(int64_t)row * nrhs + c0 + c] : 0.0;
+            acc[r][c].c = 0.0;
+        }
+    }
+    double ra[2][RES_R][2];  // [buffer][row][element of the pair]
+    auto load_step = [&](int st, int buf) {
+        const int k = st * 128 + lane * 2;
+#pragma unroll
+        for (int r = 0; r < RES_R; ++r) {
+            if (FAST && k + 1 < K) {
+                const double2 v = *(const double2 *)(ap[r] + k);
+                ra[buf][r][0] = v.x;
+                ra[buf][r][1] = v.y;
+            } else {
+                ra[buf][r][0] = k < K ? ap[r][k] : 0.0;
+                ra[buf][r][1] = k + 1 < K ? ap[r][k + 1] : 0.0;
+            }
+        }
+    };
+    auto consume = [&](int st, int buf) {
+        const int kl = (st * 128 + lane * 2) & (RES_KC - 1);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const double2 x = *(const double2 *)&sX[c][kl];
+#pragma unroll
+            for (int r = 0; r < RES_R; ++r) {
+                dd::add_product(acc[r][c], -ra[buf][r][0], x.x);
+                dd::add_product(acc[r][c], -ra[buf][r][1], x.y);
+            }
+        }
+    };
+    constexpr int SPC = RES_KC / 128;  // steps per chunk (even)
+    const int nsteps = (K + 127) / 128;
+    load_step(0, 0);
+    for (int st = 0; st < nsteps; st += 2) {
+        // two steps per trip so the register buffers index statically
+        if (st % SPC == 0) {
+            const int kc = st * 128;
+            __syncthreads();  // the previous chunk is consumed
+            for (int i = tid; i < NC * RES_KC; i += 256) {
+                const int c = i % NC, k = i / NC;
+                sX[c][k] = (kc + k < K)
+                               ? X[(int64_t)(kc + k) * nrhs + c0 + c]
+                               : 0.0;
+            }
+            __syncthreads();
+        }
+        if (st + 1 < nsteps) load_step(st + 1, 1);
+        consume(st, 0);
+        if (st + 1 < nsteps) {
+            if (st + 2 < nsteps) load_step(st + 2, 0);
+            consume(st + 1, 1);
+        }
+    }
+    // 64-lane butterfly; merge is symmetric, so every lane ends with the
+    // same pair and the order is a function of the lane ids alone
+#pragma unroll
+    for (int r = 0; r < RES_R; ++r)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                dd::Acc o;
+                o.s = __shfl_xor(acc[r][c].s, off);
+                o.c = __shfl_xor(acc[r][c].c, off);
+                dd::merge(acc[r][c], o);
+            }
+            if (lane == 0 && row0 + r < M)
+                R[(int64_t)(row0 + r) * nrhs + c0 + c] =
+                    dd::round(acc[r][c]);
+        }
+}
+
+// out[row] = sum_k |A[row][k]|: one wave per row, lanes along k, butterfly in
+// a fixed order.  max over the rows (k_colmax_abs) gives ||A||inf.
+__global__ __launch_bounds__(256) void k_row_abs_sums(
+    const double *__restrict__ A, int64_t lda, int M, int K,
+    double *__restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const double *a = A + (int64_t)row * lda;
+    double s = 0;
+    for (int k = lane; k < K; k += 64) s += fabs(a[k]);
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    if (lane == 0) out[row] = s;
+}
+
+// out[j] = max_i |V[i][j]| of an n x ncols array (ld = ncols): one block per
+// column.  A NaN in the column is returned, not skipped.
+__global__ __launch_bounds__(256) void k_colmax_abs(
+    const double *__restrict__ V, int64_t n, int ncols,
+    double *__restrict__ out) {
+    __shared__ double part[256];
+    const int tid = threadIdx.x, j = blockIdx.x;
+    auto nmax = [](double m, double a) { return (a > m || a != a) ? a : m; };
+    double m = 0;
+    for (int64_t i = tid; i < n; i += 256) m = nmax(m, fabs(V[i * ncols + j]));
+    part[tid] = m;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) part[tid] = nmax(part[tid], part[tid + w]);
+        __syncthreads();
+    }
+    if (tid == 0) out[j] = part[0];
+}
+
+// X[:, j] += D[:, j] for the columns with mask[j] != 0
+__global__ void k_axpy_masked(double *__restrict__ X,
+                              const double *__restrict__ D,
+                              const int *__restrict__ mask, int64_t n,
+                              int ncols) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         i < n * ncols; i += stride)
+        if (mask[i % ncols]) X[i] += D[i];
+}
+
 }  // namespace ck
 
 using namespace ck;
@@ -311,4 +499,68 @@ void launch_update_skinny(const double *A, int64_t lda, const double *B,
                                dim3(256), 0, s, a, lda, b, ldb, C, ldc, M,
                                nrhs, kc);
     }
+}
+
+template <int NC>
+static void launch_residual_group(const double *A, int64_t lda,
+                                  const double *X, const double *B, double *R,
+                                  int M, int K, int nrhs, int c0, bool fast,
+                                  hipStream_t s) {
+    const dim3 grid((unsigned)((M + 4 * RES_R - 1) / (4 * RES_R))), block(256);
+    if (fast)
+        hipLaunchKernelGGL((k_residual_dd<NC, true>), grid, block, 0, s, A,
+                           lda, X, B, R, M, K, nrhs, c0);
+    else
+        hipLaunchKernelGGL((k_residual_dd<NC, false>), grid, block, 0, s, A,
+                           lda, X, B, R, M, K, nrhs, c0);
+}
+
+int conflux_residual_group_width() { return RES_G; }
+
+void launch_residual_dd(const double *A, int64_t lda, const double *X,
+                        const double *B, double *R, int M, int K, int nrhs,
+                        hipStream_t s) {
+    if (M <= 0 || K <= 0 || nrhs <= 0) return;
+    const bool fast = lda % 2 == 0 && ((uintptr_t)A & 15) == 0;
+    for (int c0 = 0; c0 < nrhs; c0 += RES_G) {  // one pass over A per group
+        switch (std::min(RES_G, nrhs - c0)) {
+            case 4:
+                launch_residual_group<4>(A, lda, X, B, R, M, K, nrhs, c0,
+                                         fast, s);
+                break;
+            case 3:
+                launch_residual_group<3>(A, lda, X, B, R, M, K, nrhs, c0,
+                                         fast, s);
+                break;
+            case 2:
+                launch_residual_group<2>(A, lda, X, B, R, M, K, nrhs, c0,
+                                         fast, s);
+                break;
+            default:
+                launch_residual_group<1>(A, lda, X, B, R, M, K, nrhs, c0,
+                                         fast, s);
+        }
+    }
+}
+
+void launch_row_abs_sums(const double *A, int64_t lda, int M, int K,
+                         double *out, hipStream_t s) {
+    if (M <= 0 || K <= 0) return;
+    hipLaunchKernelGGL(k_row_abs_sums, dim3((unsigned)((M + 3) / 4)),
+                       dim3(256), 0, s, A, lda, M, K, out);
+}
+
+void launch_colmax_abs(const double *V, int64_t n, int ncols, double *out,
+                       hipStream_t s) {
+    if (n <= 0 || ncols <= 0) return;
+    hipLaunchKernelGGL(k_colmax_abs, dim3((unsigned)ncols), dim3(256), 0, s,
+                       V, n, ncols, out);
+}
+
+void launch_axpy_masked(double *X, const double *D, const int *mask,
+                        int64_t n, int ncols, hipStream_t s) {
+    if (n <= 0 || ncols <= 0) return;
+    const int64_t blocks = std::min<int64_t>((n * ncols + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_axpy_masked, dim3((unsigned)blocks), dim3(256), 0, s,
+                       X, D, mask, n, ncols);
 }

@@ -5,6 +5,16 @@ backward error against the host matrix oracle.gen_matrix(N).
 
     python tools/solve_bench.py [--N 16384] [--v 512] [--nrhs 1,16,128,512]
 
+    python tools/solve_bench.py --refine [--N 16384] [--v 512] [--nrhs 1,16,128]
+
+--refine benchmarks conflux_lu_solve_refined instead: for tournament pivoting
+and for the no-pivot fast path it prints the factorization time, the plain
+solve, the refined solve (median device ms, passes taken, worst berr before
+and after), and — once per nrhs, device-only — the time of one residual
+evaluation R = B - A X, of one of its passes over A (a pass handles one
+column group) with the effective GB/s over N^2 * 8 B, next to a plain
+device-to-device copy of the same N^2 * 8 B in the same run.
+
 CONFLUX_SOLVE_SKINNY=0|1 (read once by the library) routes the nrhs <= 16
 update through the 128-wide GEMM (0) or the skinny kernel (1);
 CONFLUX_SOLVE_BLOCK=<divisor of v> sets the sweep block (default 128 for
@@ -24,14 +34,79 @@ import conflux_amd  # noqa: E402
 from oracle import gen_matrix  # noqa: E402
 
 
+def refine_main(a):
+    import ctypes
+    lib = conflux_amd.lib()
+    rng = np.random.default_rng(0)
+    nrhs_list = [int(x) for x in (a.nrhs or "1,16,128").split(",")]
+    G = lib.conflux_lu_debug_residual_group_width()
+    with conflux_amd.Engine(a.N, a.v, 1, 1, 1, rank=-1) as e:
+        N = e.Npad
+        e.store_factors(True)
+        e.init_matrix(42)
+        Bs = {n: rng.standard_normal((N, n)) for n in nrhs_list}
+        for piv in (1, 0):
+            e.set_pivoting(piv)
+            e.factor()  # warm-up
+            fms = e.factor()
+            name = "tournament" if piv else "no-pivot"
+            print(f"N={N} v={a.v} {name}: factor {fms:.1f} ms")
+            print(f"{'nrhs':>5} {'plain ms':>9} {'refined ms':>10} {'iters':>5} "
+                  f"{'berr plain':>11} {'berr refined':>12}")
+            for nrhs in nrhs_list:
+                B = Bs[nrhs]
+                e.solve_refined(B)  # warm-up: code objects, allocator
+                tp, tr = [], []
+                for _ in range(a.reps):
+                    tp.append(e.solve(B, return_ms=True)[1])
+                    X, info = e.solve_refined(B, max_iter=a.max_iter,
+                                              return_info=True)
+                    tr.append(info["ms"])
+                b0 = e.solve_refined(B, max_iter=0,
+                                     return_info=True)[1]["berr"].max()
+                mp, mr = statistics.median(tp), statistics.median(tr)
+                print(f"{nrhs:>5} {mp:>9.3f} {mr:>10.3f} {info['iters']:>5} "
+                      f"{b0:>11.2e} {info['berr'].max():>12.2e}")
+                print(json.dumps(dict(
+                    N=N, v=a.v, nrhs=nrhs, pivoting=piv, factor_ms=fms,
+                    plain_ms_median=mp, refined_ms_median=mr,
+                    refined_ms_all=tr, iters=info["iters"], berr_plain=b0,
+                    berr_refined=float(info["berr"].max()),
+                    ferr=float(info["ferr"].max()))))
+    print(f"residual R = B - A X alone, {N} x {N}, column group {G}:")
+    print(f"{'nrhs':>5} {'resid ms':>9} {'passes':>6} {'pass ms':>8} "
+          f"{'GB/s':>8} {'copy ms':>8} {'copy GB/s (r+w)':>15}")
+    for nrhs in nrhs_list:
+        ms_r, ms_c = ctypes.c_double(), ctypes.c_double()
+        rc = lib.conflux_lu_debug_residual_dd_bench(
+            N, N, nrhs, a.reps, ctypes.byref(ms_r), ctypes.byref(ms_c))
+        assert rc == 0, rc
+        passes = -(-nrhs // G)
+        pass_ms = ms_r.value / passes
+        gbs = N * N * 8 / (pass_ms * 1e-3) / 1e9
+        cgbs = 2.0 * N * N * 8 / (ms_c.value * 1e-3) / 1e9
+        print(f"{nrhs:>5} {ms_r.value:>9.3f} {passes:>6} {pass_ms:>8.3f} "
+              f"{gbs:>8.1f} {ms_c.value:>8.3f} {cgbs:>15.1f}")
+        print(json.dumps(dict(N=N, nrhs=nrhs, resid_ms=ms_r.value,
+                              passes=passes, pass_ms=pass_ms, pass_gbs=gbs,
+                              copy_ms=ms_c.value, copy_gbs_rw=cgbs)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--N", type=int, default=16384)
     ap.add_argument("--v", type=int, default=512)
-    ap.add_argument("--nrhs", default="1,16,128,512")
+    ap.add_argument("--nrhs", default=None,
+                    help="default 1,16,128,512 (--refine: 1,16,128)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-verify", action="store_true")
+    ap.add_argument("--refine", action="store_true",
+                    help="benchmark the refined solve and its residual")
+    ap.add_argument("--max-iter", type=int, default=10)
     a = ap.parse_args()
+    if a.refine:
+        return refine_main(a)
+    a.nrhs = a.nrhs or "1,16,128,512"
     knob = os.environ.get("CONFLUX_SOLVE_SKINNY", "default")
     rng = np.random.default_rng(0)
     with conflux_amd.Engine(a.N, a.v, 1, 1, 1, rank=-1) as e:
