@@ -120,7 +120,6 @@ struct Ctx {
     bool have_comm = false;
     ncclComm_t comm{};
     ncclComm_t pcomm{};          // second comm for the lookahead panel chain
-    ncclComm_t acomm{};          // the comm the CURRENT phase must use
     bool have_pcomm = false;
     hipStream_t stream{};
     hipStream_t panel_stream{};  // lookahead stream (distributed mode)
@@ -433,46 +432,215 @@ int d2d(Ctx &c, double *dst, const double *src, int64_t n) {
     return 0;
 }
 
-// reduce-sum `count` doubles at `buf` across the pk dimension onto layer 0,
-// deterministic pk-ascending order (C1/C7; MPI_Reduce conflux_opt.hpp:636,
-// :1164).  `bufs(pk)` yields the buffer of layer pk (sim) or own (dist).
-int reduce_over_pk(Ctx &c, int pi, int pj, int64_t count,
-                   const std::function<double *(RankState &)> &bufof) {
-    if (c.Pz == 1 || count <= 0) return 0;
+// The copy layer: one function per exchange pattern, each holding its own
+// sim/dist branch.  The step functions say WHAT moves; nothing below reads
+// c.stream before it is called, so the callers' stream swaps keep working.
+using BufOf = std::function<double *(RankState &)>;
+
+// C1/C7 depth reduce (MPI_Reduce conflux_opt.hpp:636, :1164): for every item,
+// sum `count` doubles at bufof(rank) over the pk dimension of process column
+// (pi, pj) onto layer 0, in deterministic pk-ascending order.  One call is
+// one RCCL group.  `comm` is a parameter on purpose: the reduce used to read
+// a mutable "current communicator" field that every step function had to set
+// first, and the Cholesky step once forgot — its Pz>1 reduce ran on a NULL
+// communicator (caught by the shimccl 2x2x2 distributed test).
+struct ReduceItem {
+    int pi, pj;
+    int64_t count;
+    BufOf bufof;
+};
+
+int depth_reduce(Ctx &c, ncclComm_t comm, const std::vector<ReduceItem> &items) {
+    if (c.Pz == 1) return 0;
     if (c.sim) {
-        RankState &root = *get_rs(c, pi, pj, 0);
-        for (int pk = 1; pk < c.Pz; ++pk) {
-            RankState &src = *get_rs(c, pi, pj, pk);
-            launch_add2d(bufof(src), count, bufof(root), count, 1, count,
-                         c.stream);
+        for (const auto &it : items) {
+            if (it.count <= 0) continue;
+            RankState &root = *get_rs(c, it.pi, it.pj, 0);
+            for (int pk = 1; pk < c.Pz; ++pk)
+                launch_add2d(it.bufof(*get_rs(c, it.pi, it.pj, pk)), it.count,
+                             it.bufof(root), it.count, 1, it.count, c.stream);
         }
         return 0;
     }
     RankState &me = c.rs[0];
-    if (me.pi != pi || me.pj != pj) return 0;
-    if (me.pk != 0) {
-        NCCLCHK(ncclSend(bufof(me), count, ncclDouble,
-                         grank_of(c, pi, pj, 0), c.acomm, c.stream));
-    } else {
-        for (int pk = 1; pk < c.Pz; ++pk) {
-            double *tmp = me.redtmp + i64(pk - 1) * c.Ml * c.v;
-            NCCLCHK(ncclRecv(tmp, count, ncclDouble, grank_of(c, pi, pj, pk),
-                             c.acomm, c.stream));
+    auto slot = [&](int pk) { return me.redtmp + i64(pk - 1) * c.Ml * c.v; };
+    auto mine = [&](const ReduceItem &it) {
+        return it.count > 0 && it.pi == me.pi && it.pj == me.pj;
+    };
+    NCCLCHK(ncclGroupStart());
+    for (const auto &it : items) {
+        if (!mine(it)) continue;
+        if (me.pk != 0)
+            NCCLCHK(ncclSend(it.bufof(me), it.count, ncclDouble,
+                             grank_of(c, it.pi, it.pj, 0), comm, c.stream));
+        else
+            for (int pk = 1; pk < c.Pz; ++pk)
+                NCCLCHK(ncclRecv(slot(pk), it.count, ncclDouble,
+                                 grank_of(c, it.pi, it.pj, pk), comm,
+                                 c.stream));
+    }
+    NCCLCHK(ncclGroupEnd());
+    // the adds read the staged layers, so they come after the group closes
+    for (const auto &it : items)
+        if (mine(it) && me.pk == 0)
+            for (int pk = 1; pk < c.Pz; ++pk)
+                launch_add2d(slot(pk), it.count, it.bufof(me), it.count, 1,
+                             it.count, c.stream);
+    return 0;
+}
+
+// C8 column-slab spread: for each rank row pi, rows row0_of(rank)..Ml of the
+// root (pi, kcol, 0)'s A10 (v wide) go to every (pi, pj, pk)'s A10Rcv as the
+// pk-th nlayr-wide slab.  LU passes fnp (its active rows are fnp..Ml, i.e.
+// nact = Ml - fnp), Cholesky and no-pivot LU pass f2.  Rank rows with no
+// rows left move nothing; root and receivers share pi and every rank
+// derives the row count from the same plan, so the skip is symmetric.
+// Afterwards root->slabs holds the packed slabs (Cholesky's c3
+// transpose-spread reads them); with Py == Pz == 1 there is a single slab,
+// nothing is packed and A10Rcv itself is that slab.
+int spread_col_slabs(Ctx &c, int kcol,
+                     const std::function<int(const RankState &)> &row0_of) {
+    const int v = c.v, Py = c.Py, Pz = c.Pz;
+    for (auto &r : c.rs) {
+        const int f = row0_of(r), n = c.Ml - f;
+        const int64_t cnt = i64(n) * c.nlayr;
+        double *src = r.A10 + i64(f) * v;
+        if (Py == 1 && Pz == 1) {
+            launch_copy2d(src, v, r.A10Rcv, c.nlayr, n, v, c.stream);
+            continue;
         }
-        // adds must come after the group closes; caller handles via
-        // reduce_over_pk_finish
+        if (n <= 0) continue;
+        const bool root = r.pj == kcol && r.pk == 0;
+        if (c.sim) {
+            if (!root) continue;
+            launch_slab_pack(src, v, n, c.nlayr, Pz, r.slabs, c.stream);
+            for (int pj = 0; pj < Py; ++pj)
+                for (int pk = 0; pk < Pz; ++pk)
+                    if (d2d(c, get_rs(c, r.pi, pj, pk)->A10Rcv,
+                            r.slabs + pk * cnt, cnt))
+                        return CONFLUX_LU_EHIP;
+            continue;
+        }
+        NCCLCHK(ncclGroupStart());
+        if (root) {
+            launch_slab_pack(src, v, n, c.nlayr, Pz, r.slabs, c.stream);
+            for (int pj = 0; pj < Py; ++pj)
+                for (int pk = 0; pk < Pz; ++pk) {
+                    if (pj == kcol && pk == 0) continue;
+                    NCCLCHK(ncclSend(r.slabs + pk * cnt, cnt, ncclDouble,
+                                     grank_of(c, r.pi, pj, pk), c.comm,
+                                     c.stream));
+                }
+        } else {
+            NCCLCHK(ncclRecv(r.A10Rcv, cnt, ncclDouble,
+                             grank_of(c, r.pi, kcol, 0), c.comm, c.stream));
+        }
+        NCCLCHK(ncclGroupEnd());
+        if (root && d2d(c, r.A10Rcv, r.slabs, cnt)) return CONFLUX_LU_EHIP;
     }
     return 0;
 }
 
-int reduce_over_pk_finish(Ctx &c, int pi, int pj, int64_t count,
-                          const std::function<double *(RankState &)> &bufof) {
-    if (c.sim || c.Pz == 1 || count <= 0) return 0;
+// C9 row-panel spread: for each pj with w_of(pj) > 0, layer pk (nlayr rows)
+// of the root (krow, pj, 0)'s A01 (v x w, ld w) goes to A01Rcv + off_of(pj)
+// (ld Nl) on every (pi, pj, pk).  Receivers stage through redtmp.
+int spread_row_panel(Ctx &c, int krow, const std::function<int64_t(int)> &w_of,
+                     const std::function<int64_t(int)> &off_of) {
+    const int Px = c.Px, Pz = c.Pz, nl = c.nlayr;
+    for (int pj = 0; pj < c.Py; ++pj) {
+        const int64_t w = w_of(pj), off = off_of(pj);
+        if (w <= 0) continue;
+        if (c.sim) {
+            RankState &root = *get_rs(c, krow, pj, 0);
+            for (int pi = 0; pi < Px; ++pi)
+                for (int pk = 0; pk < Pz; ++pk)
+                    launch_copy2d(root.A01 + i64(pk) * nl * w, w,
+                                  get_rs(c, pi, pj, pk)->A01Rcv + off, c.Nl,
+                                  nl, w, c.stream);
+            continue;
+        }
+        RankState &me = c.rs[0];
+        if (me.pj != pj) continue;
+        const bool root = me.pi == krow && me.pk == 0;
+        NCCLCHK(ncclGroupStart());
+        if (root) {
+            for (int pi = 0; pi < Px; ++pi)
+                for (int pk = 0; pk < Pz; ++pk) {
+                    if (pi == krow && pk == 0) continue;
+                    NCCLCHK(ncclSend(me.A01 + i64(pk) * nl * w, i64(nl) * w,
+                                     ncclDouble, grank_of(c, pi, pj, pk),
+                                     c.comm, c.stream));
+                }
+        } else {
+            NCCLCHK(ncclRecv(me.redtmp, i64(nl) * w, ncclDouble,
+                             grank_of(c, krow, pj, 0), c.comm, c.stream));
+        }
+        NCCLCHK(ncclGroupEnd());
+        launch_copy2d(root ? me.A01 : me.redtmp, w, me.A01Rcv + off, c.Nl, nl,
+                      w, c.stream);
+    }
+    return 0;
+}
+
+// tile broadcast: `count` doubles at bufof(rank) go from global rank `root`
+// to the global ranks `dests` (root excluded), sends posted in that order.
+int bcast_tile(Ctx &c, const BufOf &bufof, int64_t count, int root,
+               const std::vector<int> &dests) {
+    if (c.sim) {
+        for (int g : dests)
+            if (d2d(c, bufof(c.rs[g]), bufof(c.rs[root]), count))
+                return CONFLUX_LU_EHIP;
+        return 0;
+    }
     RankState &me = c.rs[0];
-    if (me.pi != pi || me.pj != pj || me.pk != 0) return 0;
-    for (int pk = 1; pk < c.Pz; ++pk)
-        launch_add2d(me.redtmp + i64(pk - 1) * c.Ml * c.v, count, bufof(me),
-                     count, 1, count, c.stream);
+    const bool recv =
+        std::find(dests.begin(), dests.end(), me.grank) != dests.end();
+    if (dests.empty() || (me.grank != root && !recv)) return 0;
+    NCCLCHK(ncclGroupStart());
+    if (me.grank == root)
+        for (int g : dests)
+            NCCLCHK(ncclSend(bufof(me), count, ncclDouble, g, c.comm,
+                             c.stream));
+    else
+        NCCLCHK(ncclRecv(bufof(me), count, ncclDouble, root, c.comm,
+                         c.stream));
+    NCCLCHK(ncclGroupEnd());
+    return 0;
+}
+
+// barrier-fenced timed region (reference conflux_opt.hpp:531-532,1805-07):
+// fence, run `body`, fence, then surface any failed launch and fold the
+// event brackets `body` recorded into the category stats.
+int timed_region(Ctx &c, double *elapsed_ms, const std::function<int()> &body) {
+    auto fence = [&]() -> int {
+        HIPCHK(hipStreamSynchronize(c.stream));
+        if (c.have_comm) {
+            // one-element allreduce as a device barrier
+            static double *scratch = nullptr;
+            if (!scratch) HIPCHK(hipMalloc(&scratch, 8));
+            NCCLCHK(ncclAllReduce(scratch, scratch, 1, ncclDouble, ncclSum,
+                                  c.comm, c.stream));
+            HIPCHK(hipStreamSynchronize(c.stream));
+        }
+        return 0;
+    };
+    if (int rc = fence()) return rc;
+    const auto t1 = std::chrono::high_resolution_clock::now();
+    if (int rc = body()) return rc;
+    if (int rc = fence()) return rc;
+    const auto t2 = std::chrono::high_resolution_clock::now();
+    HIPCHK(hipGetLastError());  // surface any failed launch loudly
+    if (elapsed_ms)
+        *elapsed_ms =
+            std::chrono::duration<double, std::milli>(t2 - t1).count();
+    for (size_t i = 0; i < c.evs_used; ++i) {
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, c.evs[i].a, c.evs[i].b));
+        TimeCat &t = c.cats[c.evs[i].cat];
+        t.seconds += ms * 1e-3;
+        t.launches += 1;
+        t.flops += c.evs[i].flops;
+    }
     return 0;
 }
 
@@ -526,19 +694,7 @@ int factor_loop(Ctx &c, double *elapsed_ms) {
     c.evs_used = 0;
     for (auto &t : c.cats) t = TimeCat{};
 
-    // barrier-fenced timed region (reference conflux_opt.hpp:531-532,1805-07)
-    HIPCHK(hipStreamSynchronize(c.stream));
-    if (c.have_comm) {
-        // zero-byte allreduce as a device barrier
-        static double *dummy = nullptr;
-        if (!dummy) HIPCHK(hipMalloc(&dummy, 8));
-        NCCLCHK(ncclAllReduce(dummy, dummy, 1, ncclDouble, ncclSum, c.comm,
-                              c.stream));
-        HIPCHK(hipStreamSynchronize(c.stream));
-    }
-    const auto t1 = std::chrono::high_resolution_clock::now();
-
-    {
+    int rc = timed_region(c, elapsed_ms, [&]() -> int {
         StepPlan sp;
         int rc = phase01(c, 0, sp);
         if (rc) return rc;
@@ -546,31 +702,9 @@ int factor_loop(Ctx &c, double *elapsed_ms) {
             rc = run_step(c, k, sp);
             if (rc) return rc;
         }
-    }
-
-    HIPCHK(hipStreamSynchronize(c.stream));
-    if (c.have_comm) {
-        static double *dummy2 = nullptr;
-        if (!dummy2) HIPCHK(hipMalloc(&dummy2, 8));
-        NCCLCHK(ncclAllReduce(dummy2, dummy2, 1, ncclDouble, ncclSum, c.comm,
-                              c.stream));
-        HIPCHK(hipStreamSynchronize(c.stream));
-    }
-    const auto t2 = std::chrono::high_resolution_clock::now();
-    HIPCHK(hipGetLastError());  // surface any failed launch loudly
-    if (elapsed_ms)
-        *elapsed_ms =
-            std::chrono::duration<double, std::milli>(t2 - t1).count();
-
-    // fold event brackets into category stats
-    for (size_t i = 0; i < c.evs_used; ++i) {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, c.evs[i].a, c.evs[i].b));
-        TimeCat &t = c.cats[c.evs[i].cat];
-        t.seconds += ms * 1e-3;
-        t.launches += 1;
-        t.flops += c.evs[i].flops;
-    }
+        return 0;
+    });
+    if (rc) return rc;
     static int spin_stats = -1;
     if (spin_stats < 0) {
         const char *e = getenv("CONFLUX_SPIN_STATS");
@@ -588,7 +722,6 @@ int factor_loop(Ctx &c, double *elapsed_ms) {
 }
 
 int phase01(Ctx &c, int k, StepPlan &sp) {
-    c.acomm = c.pcomm;  // the panel chain's comm (may overlap main-stream ops)
     const int v = c.v, Px = c.Px, Py = c.Py, Pz = c.Pz;
     const int64_t Nl = c.Nl;
     const int loff = (k / Py) * v;
@@ -601,25 +734,17 @@ int phase01(Ctx &c, int k, StepPlan &sp) {
         launch_copy2d(r.A11 + i64(r.fnp) * Nl + loff, Nl,
                       r.A10 + i64(r.fnp) * v, v, r.nact, v, c.stream);
     }
-    if (Pz > 1) {
-        if (!c.sim) NCCLCHK(ncclGroupStart());
-        for (int pi = 0; pi < Px; ++pi) {
-            RankState *any = c.sim ? get_rs(c, pi, kcol, 0) : &c.rs[0];
-            if (!c.sim && (c.rs[0].pi != pi || c.rs[0].pj != kcol)) continue;
-            const int f = any ? any->fnp : c.rs[0].fnp;
-            const int n = any ? any->nact : c.rs[0].nact;
-            auto buf = [&, f](RankState &x) { return x.A10 + i64(f) * v; };
-            if (reduce_over_pk(c, pi, kcol, i64(n) * v, buf)) return CONFLUX_LU_ECOMM;
-        }
-        if (!c.sim) {
-            NCCLCHK(ncclGroupEnd());
-            RankState &me = c.rs[0];
-            if (me.pj == kcol) {
-                auto buf = [&](RankState &x) { return x.A10 + i64(x.fnp) * v; };
-                if (reduce_over_pk_finish(c, me.pi, kcol, i64(me.nact) * v, buf))
-                    return CONFLUX_LU_ECOMM;
-            }
-        }
+    {
+        // the panel chain's comm (it may overlap main-stream exchanges);
+        // fnp/nact are the same on every rank of a rank row
+        std::vector<ReduceItem> items;
+        for (auto &r : c.rs)
+            if (r.pj == kcol && (r.pk == 0 || !c.sim))
+                items.push_back({r.pi, kcol, i64(r.nact) * v,
+                                 [v](RankState &x) {
+                                     return x.A10 + i64(x.fnp) * v;
+                                 }});
+        if (depth_reduce(c, c.pcomm, items)) return CONFLUX_LU_ECOMM;
     }
 
     // ---- step 1: tournament pivoting --------------------------------------
@@ -803,7 +928,6 @@ int phase01(Ctx &c, int k, StepPlan &sp) {
 // identical: the column split does not reorder any K-sum).  On exit sp holds
 // step k+1's plan.
 int run_step(Ctx &c, int k, StepPlan &sp) {
-    c.acomm = c.comm;
     const int v = c.v, Px = c.Px, Py = c.Py, Pz = c.Pz;
     const int64_t Nl = c.Nl;
     const int loff = (k / Py) * v;
@@ -812,7 +936,6 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
     const bool look = (k + 1 < c.Nt);
     const int ncol = (k + 1) % Py;
     const int64_t lnext = i64(v) * ((k + 1) / Py);
-    (void)kcol;
 
     // ---- step 2: push pivot rows up, pack, depth-reduce (C7) --------------
     for (auto &r : c.rs) {
@@ -886,25 +1009,13 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
         launch_copy2d(r.A11 + i64(f) * Nl + loff, Nl, r.A01pack, wA01, cnt,
                       wA01, c.stream);
     }
-    if (Pz > 1) {
-        if (!c.sim) NCCLCHK(ncclGroupStart());
-        for (int pi = 0; pi < Px; ++pi) {
-            const int cnt = (int)sp.lrows[pi].size();
-            for (int pj = 0; pj < Py; ++pj) {
-                if (!c.sim && (c.rs[0].pi != pi || c.rs[0].pj != pj)) continue;
-                auto buf = [](RankState &x) { return x.A01pack; };
-                if (reduce_over_pk(c, pi, pj, i64(cnt) * wA01, buf))
-                    return CONFLUX_LU_ECOMM;
-            }
-        }
-        if (!c.sim) {
-            NCCLCHK(ncclGroupEnd());
-            RankState &me = c.rs[0];
-            auto buf = [](RankState &x) { return x.A01pack; };
-            if (reduce_over_pk_finish(c, me.pi, me.pj,
-                                      i64(sp.lrows[me.pi].size()) * wA01, buf))
-                return CONFLUX_LU_ECOMM;
-        }
+    {
+        std::vector<ReduceItem> items;
+        for (int pi = 0; pi < Px; ++pi)
+            for (int pj = 0; pj < Py; ++pj)
+                items.push_back({pi, pj, i64(sp.lrows[pi].size()) * wA01,
+                                 [](RankState &x) { return x.A01pack; }});
+        if (depth_reduce(c, c.comm, items)) return CONFLUX_LU_ECOMM;
     }
 
     // ---- step 3: route packed pivot rows to row krow, pivot-ordered (C5/C6)
@@ -1057,6 +1168,22 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
     }
     const bool slice_first =
         split_trsm && slice_env && Pz == 1 && Px == 1 && look;
+    // store_factors: the solved U rows (and the diagonal tile) go to Fres,
+    // on whichever stream the solve ran
+    auto store_u = [&](RankState &r) {
+        if (!c.store_factors) return;
+        double *Frow = r.Fres + i64(k / Px) * v * Nl;  // local row tile of k
+        // U region starts at this rank's first local column tile with
+        // global tile >= k; columns left of it carry stale already-factored
+        // data the reference never reads (cf. oracle lu_oracle.py step-5
+        // `gcs >= off` mask)
+        const int64_t ustart = i64(v) * (r.pj < kcol ? k / Py + 1 : k / Py);
+        if (Nl - ustart > 0)
+            launch_copy2d(r.A01 + (ustart - loff), wA01, Frow + ustart, Nl, v,
+                          Nl - ustart, c.stream);
+        if (r.pj == kcol)  // diagonal tile: packed LU from A00
+            launch_copy2d(r.A00, v, Frow + loff, Nl, v, v, c.stream);
+    };
     if (split_trsm) {
         HIPCHK(hipEventRecord(c.ev_t3, c.stream));
         HIPCHK(hipStreamWaitEvent(c.trsm_stream, c.ev_t3, 0));
@@ -1077,18 +1204,7 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
                     return CONFLUX_LU_EINTERNAL;
             } else if (trsm_left_lower(c, r, r.A01, wA01, wA01))
                 return CONFLUX_LU_EINTERNAL;
-            if (c.store_factors) {
-                const int ltik = k / Px;
-                const int64_t ustart =
-                    i64(v) * (r.pj < kcol ? k / Py + 1 : k / Py);
-                if (Nl - ustart > 0)
-                    launch_copy2d(r.A01 + (ustart - loff), wA01,
-                                  r.Fres + i64(ltik) * v * Nl + ustart, Nl, v,
-                                  Nl - ustart, c.stream);
-                if (r.pj == kcol)
-                    launch_copy2d(r.A00, v, r.Fres + i64(ltik) * v * Nl + loff,
-                                  Nl, v, v, c.stream);
-            }
+            store_u(r);
         }
         HIPCHK(hipEventRecord(c.ev_t5, c.stream));
         c.stream = saved;
@@ -1109,61 +1225,9 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
                           r.A10hist + i64(r.fnp) * Nl + loff, Nl, r.nact, v,
                           c.stream);
     }
-    // spread
-    if (Pz == 1 && Py == 1) {
-        // degenerate: A10Rcv = post-trsm A10 active rows (alias by copy)
-        RankState &r = c.rs[0];
-        if (c.sim)
-            for (auto &x : c.rs)
-                launch_copy2d(x.A10 + i64(x.fnp) * v, v, x.A10Rcv, c.nlayr,
-                              x.nact, v, c.stream);
-        else
-            launch_copy2d(r.A10 + i64(r.fnp) * v, v, r.A10Rcv, c.nlayr, r.nact,
-                          v, c.stream);
-    } else {
-        for (int pi = 0; pi < Px; ++pi) {
-            RankState *root = get_rs(c, pi, kcol, 0);
-            if (c.sim) {
-                const int n = root->nact;
-                launch_slab_pack(root->A10 + i64(root->fnp) * v, v, n, c.nlayr,
-                                 Pz, root->slabs, c.stream);
-                for (int pj = 0; pj < Py; ++pj)
-                    for (int pk = 0; pk < Pz; ++pk) {
-                        RankState &d = *get_rs(c, pi, pj, pk);
-                        if (d2d(c, d.A10Rcv,
-                                root->slabs + i64(pk) * n * c.nlayr,
-                                i64(n) * c.nlayr))
-                            return CONFLUX_LU_EHIP;
-                    }
-            } else {
-                RankState &me = c.rs[0];
-                if (me.pi != pi) continue;
-                const int n = me.nact;
-                NCCLCHK(ncclGroupStart());
-                if (root && root->grank == me.grank) {
-                    launch_slab_pack(me.A10 + i64(me.fnp) * v, v, n, c.nlayr,
-                                     Pz, me.slabs, c.stream);
-                    for (int pj = 0; pj < Py; ++pj)
-                        for (int pk = 0; pk < Pz; ++pk) {
-                            if (pj == kcol && pk == 0) continue;
-                            NCCLCHK(ncclSend(me.slabs + i64(pk) * n * c.nlayr,
-                                             i64(n) * c.nlayr, ncclDouble,
-                                             grank_of(c, pi, pj, pk), c.comm,
-                                             c.stream));
-                        }
-                } else {
-                    NCCLCHK(ncclRecv(me.A10Rcv, i64(n) * c.nlayr, ncclDouble,
-                                     grank_of(c, pi, kcol, 0), c.comm,
-                                     c.stream));
-                }
-                NCCLCHK(ncclGroupEnd());
-                if (root && root->grank == me.grank)
-                    if (d2d(c, me.A10Rcv, me.slabs + i64(0) * n * c.nlayr,
-                            i64(n) * c.nlayr))
-                        return CONFLUX_LU_EHIP;
-            }
-        }
-    }
+    if (int rc = spread_col_slabs(
+            c, kcol, [](const RankState &r) { return r.fnp; }))
+        return rc;
 
     // ---- step 5: A01 <- L^-1 A01 (already issued on the second stream
     // when split_trsm; the C9 spread below waits for it), spread (C9) -------
@@ -1172,23 +1236,7 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
             if (r.pi != krow || r.pk != 0) continue;
             if (trsm_left_lower(c, r, r.A01, wA01, wA01))
                 return CONFLUX_LU_EINTERNAL;
-            if (c.store_factors) {
-                const int ltik = k / Px;
-                // U region starts at this rank's first local column tile
-                // with global tile >= k; columns left of it carry stale
-                // already-factored data the reference never reads
-                // (cf. oracle lu_oracle.py step-5 `gcs >= off` mask)
-                const int64_t ustart =
-                    i64(v) * (r.pj < kcol ? k / Py + 1 : k / Py);
-                if (Nl - ustart > 0)
-                    launch_copy2d(r.A01 + (ustart - loff), wA01,
-                                  r.Fres + i64(ltik) * v * Nl + ustart, Nl, v,
-                                  Nl - ustart, c.stream);
-                if (r.pj == kcol)  // diagonal tile: packed LU from A00
-                    launch_copy2d(r.A00, v,
-                                  r.Fres + i64(ltik) * v * Nl + loff, Nl, v,
-                                  v, c.stream);
-            }
+            store_u(r);
         }
     } else if (!slice_first) {
         HIPCHK(hipStreamWaitEvent(c.stream, c.ev_t5, 0));
@@ -1208,45 +1256,10 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
                           c.stream);
         } else
             launch_copy2d(r.A01, wA01, r.A01Rcv, Nl, c.nlayr, wA01, c.stream);
-    } else {
-        for (int pj = 0; pj < Py; ++pj) {
-            RankState *root = get_rs(c, krow, pj, 0);
-            if (c.sim) {
-                for (int pi = 0; pi < Px; ++pi)
-                    for (int pk = 0; pk < Pz; ++pk) {
-                        RankState &d = *get_rs(c, pi, pj, pk);
-                        launch_copy2d(root->A01 + i64(pk) * c.nlayr * wA01,
-                                      wA01, d.A01Rcv, Nl, c.nlayr, wA01,
-                                      c.stream);
-                    }
-            } else {
-                RankState &me = c.rs[0];
-                if (me.pj != pj) continue;
-                NCCLCHK(ncclGroupStart());
-                if (root && root->grank == me.grank) {
-                    for (int pi = 0; pi < Px; ++pi)
-                        for (int pk = 0; pk < Pz; ++pk) {
-                            if (pi == krow && pk == 0) continue;
-                            NCCLCHK(ncclSend(
-                                me.A01 + i64(pk) * c.nlayr * wA01,
-                                i64(c.nlayr) * wA01, ncclDouble,
-                                grank_of(c, pi, pj, pk), c.comm, c.stream));
-                        }
-                } else {
-                    NCCLCHK(ncclRecv(me.redtmp, i64(c.nlayr) * wA01,
-                                     ncclDouble, grank_of(c, krow, pj, 0),
-                                     c.comm, c.stream));
-                }
-                NCCLCHK(ncclGroupEnd());
-                if (root && root->grank == me.grank)
-                    launch_copy2d(me.A01, wA01, me.A01Rcv, Nl, c.nlayr, wA01,
-                                  c.stream);
-                else
-                    launch_copy2d(me.redtmp, wA01, me.A01Rcv, Nl, c.nlayr,
-                                  wA01, c.stream);
-            }
-        }
-    }
+    } else if (int rc = spread_row_panel(
+                   c, krow, [&](int) { return wA01; },
+                   [](int) { return int64_t(0); }))
+        return rc;
 
     // ---- step 6: trailing update (the flop carrier), split for lookahead --
     auto gemm_piece = [&](RankState &r, int64_t col0, int64_t ncols,
@@ -1379,10 +1392,20 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
 //   c4  A_ij -= L_ik * L_jk^T for local tiles with i >= j > k (NT GEMM)
 // No pivoting -> row activation is static: rows of tiles < t owned by pi.
 // ===========================================================================
-namespace {
-
 inline int ntiles_lt(const Ctx &c, int pi, int t) {
     return (t <= pi) ? 0 : (t - pi + c.Px - 1) / c.Px;
+}
+
+// depth-reduce items of the k-th tile column under static row activation
+// (Cholesky c0, no-pivot n0): rank row pi reduces its rows of tiles >= k
+std::vector<ReduceItem> static_col_items(const Ctx &c, int k) {
+    std::vector<ReduceItem> items;
+    for (int pi = 0; pi < c.Px; ++pi) {
+        const int v = c.v, f = v * ntiles_lt(c, pi, k);
+        items.push_back({pi, k % c.Py, i64(c.Ml - f) * v,
+                         [f, v](RankState &x) { return x.A10 + i64(f) * v; }});
+    }
+    return items;
 }
 
 int potrf_tile(Ctx &c, double *T, int64_t ld) {
@@ -1426,9 +1449,6 @@ int trsm_right_lowT(Ctx &c, RankState &r, double *X, int64_t ldx, int M) {
 }
 
 int chol_step(Ctx &c, int k) {
-    c.acomm = c.comm;  // reduce_over_pk sends on acomm; without this the
-                       // Pz>1 depth reduce ran on a NULL communicator
-                       // (caught by the shimccl 2x2x2 distributed test)
     const int v = c.v, Px = c.Px, Py = c.Py, Pz = c.Pz, Nt = c.Nt;
     const int64_t Nl = c.Nl;
     const int kcol = k % Py, krow = k % Px;
@@ -1443,27 +1463,7 @@ int chol_step(Ctx &c, int k) {
         launch_copy2d(r.A11 + i64(f) * Nl + loff, Nl, r.A10 + i64(f) * v, v,
                       c.Ml - f, v, c.stream);
     }
-    if (Pz > 1) {
-        if (!c.sim) NCCLCHK(ncclGroupStart());
-        for (int pi = 0; pi < Px; ++pi) {
-            if (!c.sim && (c.rs[0].pi != pi || c.rs[0].pj != kcol)) continue;
-            const int f = fnp_of(pi);
-            auto buf = [&, f](RankState &x) { return x.A10 + i64(f) * v; };
-            if (reduce_over_pk(c, pi, kcol, i64(c.Ml - f) * v, buf))
-                return CONFLUX_LU_ECOMM;
-        }
-        if (!c.sim) {
-            NCCLCHK(ncclGroupEnd());
-            RankState &me = c.rs[0];
-            if (me.pj == kcol) {
-                const int f = fnp_of(me.pi);
-                auto buf = [&, f](RankState &x) { return x.A10 + i64(f) * v; };
-                if (reduce_over_pk_finish(c, me.pi, kcol, i64(c.Ml - f) * v,
-                                          buf))
-                    return CONFLUX_LU_ECOMM;
-            }
-        }
-    }
+    if (depth_reduce(c, c.comm, static_col_items(c, k))) return CONFLUX_LU_ECOMM;
 
     // ---- c1: potrf diagonal tile; broadcast L_kk down the column ----------
     {
@@ -1475,30 +1475,12 @@ int chol_step(Ctx &c, int k) {
             launch_copy2d(own->A10 + i64(fd) * v, v, own->A00, v, v, v,
                           c.stream);
         }
-        if (c.sim) {
-            for (int pi = 0; pi < Px; ++pi) {
-                if (pi == krow) continue;
-                RankState &d = *get_rs(c, pi, kcol, 0);
-                if (d2d(c, d.A00, own->A00, i64(v) * v)) return CONFLUX_LU_EHIP;
-            }
-        } else {
-            RankState &me = c.rs[0];
-            if (me.pj == kcol && me.pk == 0 && Px > 1) {
-                NCCLCHK(ncclGroupStart());
-                if (me.pi == krow) {
-                    for (int pi = 0; pi < Px; ++pi)
-                        if (pi != krow)
-                            NCCLCHK(ncclSend(me.A00, i64(v) * v, ncclDouble,
-                                             grank_of(c, pi, kcol, 0), c.comm,
-                                             c.stream));
-                } else {
-                    NCCLCHK(ncclRecv(me.A00, i64(v) * v, ncclDouble,
-                                     grank_of(c, krow, kcol, 0), c.comm,
-                                     c.stream));
-                }
-                NCCLCHK(ncclGroupEnd());
-            }
-        }
+        std::vector<int> dests;  // layer 0 of process column kcol
+        for (int pi = 0; pi < Px; ++pi)
+            if (pi != krow) dests.push_back(grank_of(c, pi, kcol, 0));
+        if (int rc = bcast_tile(c, [](RankState &x) { return x.A00; },
+                                i64(v) * v, grank_of(c, krow, kcol, 0), dests))
+            return rc;
     }
 
     // ---- c2: column TRSM (strictly below the diagonal); store L -----------
@@ -1522,56 +1504,9 @@ int chol_step(Ctx &c, int k) {
     }
 
     // ---- c2b: slab-spread the L panel over (pj, pk)  [= LU C8] ------------
-    if (Py == 1 && Pz == 1) {
-        for (auto &r : c.rs) {
-            const int f2 = f2_of(r.pi);
-            launch_copy2d(r.A10 + i64(f2) * v, v, r.A10Rcv, c.nlayr,
-                          c.Ml - f2, v, c.stream);
-        }
-    } else {
-        for (int pi = 0; pi < Px; ++pi) {
-            RankState *root = get_rs(c, pi, kcol, 0);
-            const int f2 = f2_of(pi);
-            const int n2 = c.Ml - f2;
-            if (c.sim) {
-                if (n2 > 0)
-                    launch_slab_pack(root->A10 + i64(f2) * v, v, n2, c.nlayr,
-                                     Pz, root->slabs, c.stream);
-                for (int pj = 0; pj < Py; ++pj)
-                    for (int pk = 0; pk < Pz; ++pk) {
-                        RankState &d = *get_rs(c, pi, pj, pk);
-                        if (n2 > 0 &&
-                            d2d(c, d.A10Rcv, root->slabs + i64(pk) * n2 * c.nlayr,
-                                i64(n2) * c.nlayr))
-                            return CONFLUX_LU_EHIP;
-                    }
-            } else {
-                RankState &me = c.rs[0];
-                if (me.pi != pi || n2 <= 0) continue;
-                NCCLCHK(ncclGroupStart());
-                if (root && root->grank == me.grank) {
-                    launch_slab_pack(me.A10 + i64(f2) * v, v, n2, c.nlayr, Pz,
-                                     me.slabs, c.stream);
-                    for (int pj = 0; pj < Py; ++pj)
-                        for (int pk = 0; pk < Pz; ++pk) {
-                            if (pj == kcol && pk == 0) continue;
-                            NCCLCHK(ncclSend(me.slabs + i64(pk) * n2 * c.nlayr,
-                                             i64(n2) * c.nlayr, ncclDouble,
-                                             grank_of(c, pi, pj, pk), c.comm,
-                                             c.stream));
-                        }
-                } else {
-                    NCCLCHK(ncclRecv(me.A10Rcv, i64(n2) * c.nlayr, ncclDouble,
-                                     grank_of(c, pi, kcol, 0), c.comm,
-                                     c.stream));
-                }
-                NCCLCHK(ncclGroupEnd());
-                if (root && root->grank == me.grank)
-                    if (d2d(c, me.A10Rcv, me.slabs, i64(n2) * c.nlayr))
-                        return CONFLUX_LU_EHIP;
-            }
-        }
-    }
+    if (int rc = spread_col_slabs(
+            c, kcol, [&](const RankState &r) { return f2_of(r.pi); }))
+        return rc;
 
     // ---- c3: transpose-spread L_jk slabs to the columns that need them ----
     // destination layout: A01Rcv as [local col tile][v][nlayr]
@@ -1789,29 +1724,8 @@ int chol_c4_1r(Ctx &c, int k, double *rcvA, double *rcvB, bool slice_only,
     return 0;
 }
 
-int chol_loop(Ctx &c, double *elapsed_ms) {
-    for (auto &r : c.rs) {
-        if (c.store_factors) {
-            if (ensure_factor_bufs(c, r, /*need_hist=*/false))
-                return CONFLUX_LU_EHIP;
-            launch_zero2d(r.Fres, c.Nl, c.Ml, c.Nl, c.stream);
-        }
-    }
-    // perm is identity for the pivotless path (API consistency)
-    c.pivotInds.resize(c.M);
-    std::iota(c.pivotInds.begin(), c.pivotInds.end(), 0);
-    c.evs_used = 0;
-    for (auto &t : c.cats) t = TimeCat{};
-
-    HIPCHK(hipStreamSynchronize(c.stream));
-    if (c.have_comm) {
-        static double *dummy = nullptr;
-        if (!dummy) HIPCHK(hipMalloc(&dummy, 8));
-        NCCLCHK(ncclAllReduce(dummy, dummy, 1, ncclDouble, ncclSum, c.comm,
-                              c.stream));
-        HIPCHK(hipStreamSynchronize(c.stream));
-    }
-    const auto t1 = std::chrono::high_resolution_clock::now();
+// every step of one Cholesky factorization (the timed body of chol_loop)
+int chol_steps(Ctx &c) {
     static int chol_look = -1;
     if (chol_look < 0) {
         const char *e = getenv("CONFLUX_CHOL_LOOK");
@@ -1851,31 +1765,24 @@ int chol_loop(Ctx &c, double *elapsed_ms) {
             if (rc) return rc;
         }
     }
-    HIPCHK(hipStreamSynchronize(c.stream));
-    if (c.have_comm) {
-        static double *dummy2 = nullptr;
-        if (!dummy2) HIPCHK(hipMalloc(&dummy2, 8));
-        NCCLCHK(ncclAllReduce(dummy2, dummy2, 1, ncclDouble, ncclSum, c.comm,
-                              c.stream));
-        HIPCHK(hipStreamSynchronize(c.stream));
-    }
-    const auto t2 = std::chrono::high_resolution_clock::now();
-    HIPCHK(hipGetLastError());  // surface any failed launch loudly
-    if (elapsed_ms)
-        *elapsed_ms =
-            std::chrono::duration<double, std::milli>(t2 - t1).count();
-    for (size_t i = 0; i < c.evs_used; ++i) {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, c.evs[i].a, c.evs[i].b));
-        TimeCat &t = c.cats[c.evs[i].cat];
-        t.seconds += ms * 1e-3;
-        t.launches += 1;
-        t.flops += c.evs[i].flops;
-    }
     return 0;
 }
 
-}  // namespace
+int chol_loop(Ctx &c, double *elapsed_ms) {
+    for (auto &r : c.rs) {
+        if (c.store_factors) {
+            if (ensure_factor_bufs(c, r, /*need_hist=*/false))
+                return CONFLUX_LU_EHIP;
+            launch_zero2d(r.Fres, c.Nl, c.Ml, c.Nl, c.stream);
+        }
+    }
+    // perm is identity for the pivotless path (API consistency)
+    c.pivotInds.resize(c.M);
+    std::iota(c.pivotInds.begin(), c.pivotInds.end(), 0);
+    c.evs_used = 0;
+    for (auto &t : c.cats) t = TimeCat{};
+    return timed_region(c, elapsed_ms, [&] { return chol_steps(c); });
+}
 
 }  // namespace
 
@@ -1899,8 +1806,7 @@ int chol_loop(Ctx &c, double *elapsed_ms) {
 namespace {
 
 int nopiv_step(Ctx &c, int k) {
-    c.acomm = c.comm;
-    const int v = c.v, Px = c.Px, Py = c.Py, Pz = c.Pz;
+    const int v = c.v, Px = c.Px, Py = c.Py;
     const int64_t Nl = c.Nl;
     const int kcol = k % Py, krow = k % Px;
     const int64_t loff = i64(k / Py) * v;
@@ -1915,27 +1821,7 @@ int nopiv_step(Ctx &c, int k) {
         launch_copy2d(r.A11 + i64(f) * Nl + loff, Nl, r.A10 + i64(f) * v, v,
                       c.Ml - f, v, c.stream);
     }
-    if (Pz > 1) {
-        if (!c.sim) NCCLCHK(ncclGroupStart());
-        for (int pi = 0; pi < Px; ++pi) {
-            if (!c.sim && (c.rs[0].pi != pi || c.rs[0].pj != kcol)) continue;
-            const int f = fnp_of(pi);
-            auto buf = [&, f](RankState &x) { return x.A10 + i64(f) * v; };
-            if (reduce_over_pk(c, pi, kcol, i64(c.Ml - f) * v, buf))
-                return CONFLUX_LU_ECOMM;
-        }
-        if (!c.sim) {
-            NCCLCHK(ncclGroupEnd());
-            RankState &me = c.rs[0];
-            if (me.pj == kcol) {
-                const int f = fnp_of(me.pi);
-                auto buf = [&, f](RankState &x) { return x.A10 + i64(f) * v; };
-                if (reduce_over_pk_finish(c, me.pi, kcol, i64(c.Ml - f) * v,
-                                          buf))
-                    return CONFLUX_LU_ECOMM;
-            }
-        }
-    }
+    if (depth_reduce(c, c.comm, static_col_items(c, k))) return CONFLUX_LU_ECOMM;
 
     // ---- n1: blocked no-pivot LU of the diagonal tile; broadcast A00 -----
     {
@@ -1966,27 +1852,13 @@ int nopiv_step(Ctx &c, int k) {
             launch_copy2d(T, v, own->A00, v, v, v, c.stream);
         }
         // broadcast the packed LU to every rank (both halves are consumed)
-        if (c.sim) {
-            RankState &src = *get_rs(c, krow, kcol, 0);
-            for (auto &d : c.rs)
-                if (&d != &src)
-                    if (d2d(c, d.A00, src.A00, i64(v) * v))
-                        return CONFLUX_LU_EHIP;
-        } else if (c.world > 1) {
-            RankState &me = c.rs[0];
-            NCCLCHK(ncclGroupStart());
-            if (own && own->grank == me.grank) {
-                for (int g = 0; g < c.world; ++g)
-                    if (g != me.grank)
-                        NCCLCHK(ncclSend(me.A00, i64(v) * v, ncclDouble, g,
-                                         c.comm, c.stream));
-            } else {
-                NCCLCHK(ncclRecv(me.A00, i64(v) * v, ncclDouble,
-                                 grank_of(c, krow, kcol, 0), c.comm,
-                                 c.stream));
-            }
-            NCCLCHK(ncclGroupEnd());
-        }
+        const int root = grank_of(c, krow, kcol, 0);
+        std::vector<int> dests;
+        for (int g = 0; g < c.world; ++g)
+            if (g != root) dests.push_back(g);
+        if (int rc = bcast_tile(c, [](RankState &x) { return x.A00; },
+                                i64(v) * v, root, dests))
+            return rc;
     }
 
     // ---- n2: A10 <- A10 U^-1 below the diagonal; store L; C8 spread ------
@@ -2006,57 +1878,9 @@ int nopiv_step(Ctx &c, int k) {
                               Nl, v, v, c.stream);
         }
     }
-    if (Py == 1 && Pz == 1) {
-        for (auto &r : c.rs) {
-            const int f2 = f2_of(r.pi);
-            launch_copy2d(r.A10 + i64(f2) * v, v, r.A10Rcv, c.nlayr,
-                          c.Ml - f2, v, c.stream);
-        }
-    } else {
-        for (int pi = 0; pi < Px; ++pi) {
-            RankState *root = get_rs(c, pi, kcol, 0);
-            const int f2 = f2_of(pi);
-            const int n2 = c.Ml - f2;
-            if (c.sim) {
-                if (n2 > 0)
-                    launch_slab_pack(root->A10 + i64(f2) * v, v, n2, c.nlayr,
-                                     Pz, root->slabs, c.stream);
-                for (int pj = 0; pj < Py; ++pj)
-                    for (int pk = 0; pk < Pz; ++pk) {
-                        RankState &d = *get_rs(c, pi, pj, pk);
-                        if (n2 > 0 &&
-                            d2d(c, d.A10Rcv,
-                                root->slabs + i64(pk) * n2 * c.nlayr,
-                                i64(n2) * c.nlayr))
-                            return CONFLUX_LU_EHIP;
-                    }
-            } else {
-                RankState &me = c.rs[0];
-                if (me.pi != pi || n2 <= 0) continue;
-                NCCLCHK(ncclGroupStart());
-                if (root && root->grank == me.grank) {
-                    launch_slab_pack(me.A10 + i64(f2) * v, v, n2, c.nlayr, Pz,
-                                     me.slabs, c.stream);
-                    for (int pj = 0; pj < Py; ++pj)
-                        for (int pk = 0; pk < Pz; ++pk) {
-                            if (pj == kcol && pk == 0) continue;
-                            NCCLCHK(ncclSend(me.slabs + i64(pk) * n2 * c.nlayr,
-                                             i64(n2) * c.nlayr, ncclDouble,
-                                             grank_of(c, pi, pj, pk), c.comm,
-                                             c.stream));
-                        }
-                } else {
-                    NCCLCHK(ncclRecv(me.A10Rcv, i64(n2) * c.nlayr, ncclDouble,
-                                     grank_of(c, pi, kcol, 0), c.comm,
-                                     c.stream));
-                }
-                NCCLCHK(ncclGroupEnd());
-                if (root && root->grank == me.grank)
-                    if (d2d(c, me.A10Rcv, me.slabs, i64(n2) * c.nlayr))
-                        return CONFLUX_LU_EHIP;
-            }
-        }
-    }
+    if (int rc = spread_col_slabs(
+            c, kcol, [&](const RankState &r) { return f2_of(r.pi); }))
+        return rc;
 
     // ---- n3: A01 row panel (diag-tile rows, cols > k): reduce, solve,
     // store U, C9 spread ----------------------------------------------------
@@ -2068,27 +1892,12 @@ int nopiv_step(Ctx &c, int k) {
         launch_copy2d(r.A11 + i64(fnp_of(krow)) * Nl + c0, Nl, r.A01, w, v, w,
                       c.stream);
     }
-    if (Pz > 1) {
-        if (!c.sim) NCCLCHK(ncclGroupStart());
-        for (int pj = 0; pj < Py; ++pj) {
-            if (!c.sim && (c.rs[0].pi != krow || c.rs[0].pj != pj)) continue;
-            const int64_t w = Nl - i64(ltj0_of(pj)) * v;
-            if (w <= 0) continue;
-            auto buf = [](RankState &x) { return x.A01; };
-            if (reduce_over_pk(c, krow, pj, i64(c.v) * w, buf))
-                return CONFLUX_LU_ECOMM;
-        }
-        if (!c.sim) {
-            NCCLCHK(ncclGroupEnd());
-            RankState &me = c.rs[0];
-            if (me.pi == krow) {
-                const int64_t w = Nl - i64(ltj0_of(me.pj)) * v;
-                auto buf = [](RankState &x) { return x.A01; };
-                if (w > 0 &&
-                    reduce_over_pk_finish(c, krow, me.pj, i64(c.v) * w, buf))
-                    return CONFLUX_LU_ECOMM;
-            }
-        }
+    {
+        std::vector<ReduceItem> items;
+        for (int pj = 0; pj < Py; ++pj)
+            items.push_back({krow, pj, v * (Nl - i64(ltj0_of(pj)) * v),
+                             [](RankState &x) { return x.A01; }});
+        if (depth_reduce(c, c.comm, items)) return CONFLUX_LU_ECOMM;
     }
     for (auto &r : c.rs) {
         if (r.pi != krow || r.pk != 0) continue;
@@ -2102,44 +1911,10 @@ int nopiv_step(Ctx &c, int k) {
     }
     // C9: spread the solved row panel down each column (into A01Rcv at the
     // SAME local column offset, ld Nl)
-    for (int pj = 0; pj < Py; ++pj) {
-        const int64_t c0 = i64(ltj0_of(pj)) * v;
-        const int64_t w = Nl - c0;
-        if (w <= 0) continue;
-        RankState *root = get_rs(c, krow, pj, 0);
-        if (c.sim) {
-            for (int pi = 0; pi < Px; ++pi)
-                for (int pk = 0; pk < Pz; ++pk) {
-                    RankState &d = *get_rs(c, pi, pj, pk);
-                    launch_copy2d(root->A01 + i64(pk) * c.nlayr * w, w,
-                                  d.A01Rcv + c0, Nl, c.nlayr, w, c.stream);
-                }
-        } else {
-            RankState &me = c.rs[0];
-            if (me.pj != pj) continue;
-            NCCLCHK(ncclGroupStart());
-            if (root && root->grank == me.grank) {
-                for (int pi = 0; pi < Px; ++pi)
-                    for (int pk = 0; pk < Pz; ++pk) {
-                        if (pi == krow && pk == 0) continue;
-                        NCCLCHK(ncclSend(me.A01 + i64(pk) * c.nlayr * w,
-                                         i64(c.nlayr) * w, ncclDouble,
-                                         grank_of(c, pi, pj, pk), c.comm,
-                                         c.stream));
-                    }
-            } else {
-                NCCLCHK(ncclRecv(me.redtmp, i64(c.nlayr) * w, ncclDouble,
-                                 grank_of(c, krow, pj, 0), c.comm, c.stream));
-            }
-            NCCLCHK(ncclGroupEnd());
-            if (root && root->grank == me.grank)
-                launch_copy2d(me.A01, w, me.A01Rcv + c0, Nl, c.nlayr, w,
-                              c.stream);
-            else
-                launch_copy2d(me.redtmp, w, me.A01Rcv + c0, Nl, c.nlayr, w,
-                              c.stream);
-        }
-    }
+    if (int rc = spread_row_panel(
+            c, krow, [&](int pj) { return Nl - i64(ltj0_of(pj)) * v; },
+            [&](int pj) { return i64(ltj0_of(pj)) * v; }))
+        return rc;
 
     // ---- n4: one rectangular trailing update per rank ---------------------
     for (auto &r : c.rs) {
@@ -2171,41 +1946,13 @@ int nopiv_loop(Ctx &c, double *elapsed_ms) {
     std::iota(c.pivotInds.begin(), c.pivotInds.end(), 0);
     c.evs_used = 0;
     for (auto &t : c.cats) t = TimeCat{};
-    HIPCHK(hipStreamSynchronize(c.stream));
-    if (c.have_comm) {
-        static double *dummy = nullptr;
-        if (!dummy) HIPCHK(hipMalloc(&dummy, 8));
-        NCCLCHK(ncclAllReduce(dummy, dummy, 1, ncclDouble, ncclSum, c.comm,
-                              c.stream));
-        HIPCHK(hipStreamSynchronize(c.stream));
-    }
-    const auto t1 = std::chrono::high_resolution_clock::now();
-    for (int k = 0; k < c.Nt; ++k) {
-        int rc = nopiv_step(c, k);
-        if (rc) return rc;
-    }
-    HIPCHK(hipStreamSynchronize(c.stream));
-    if (c.have_comm) {
-        static double *dummy2 = nullptr;
-        if (!dummy2) HIPCHK(hipMalloc(&dummy2, 8));
-        NCCLCHK(ncclAllReduce(dummy2, dummy2, 1, ncclDouble, ncclSum, c.comm,
-                              c.stream));
-        HIPCHK(hipStreamSynchronize(c.stream));
-    }
-    const auto t2 = std::chrono::high_resolution_clock::now();
-    HIPCHK(hipGetLastError());
-    if (elapsed_ms)
-        *elapsed_ms =
-            std::chrono::duration<double, std::milli>(t2 - t1).count();
-    for (size_t i = 0; i < c.evs_used; ++i) {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, c.evs[i].a, c.evs[i].b));
-        TimeCat &t = c.cats[c.evs[i].cat];
-        t.seconds += ms * 1e-3;
-        t.launches += 1;
-        t.flops += c.evs[i].flops;
-    }
-    return 0;
+    return timed_region(c, elapsed_ms, [&]() -> int {
+        for (int k = 0; k < c.Nt; ++k) {
+            int rc = nopiv_step(c, k);
+            if (rc) return rc;
+        }
+        return 0;
+    });
 }
 
 }  // namespace

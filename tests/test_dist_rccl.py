@@ -193,6 +193,17 @@ def test_dist_nopivot(tmp_path):
         assert float(res["resid"]) < 1e-14
     F = _assemble_F(results, N, v, Px, Py, Pz)
     assert np.abs(F - ref).max() < 1e-11 * np.abs(ref).max()
+    # ... and BIT-IDENTICAL to simulation mode, as for tournament LU above:
+    # both modes go through the same transport helpers, so any divergence
+    # is a transport ordering bug
+    from conflux_amd import Engine
+    with Engine(N, v, Px, Py, Pz, rank=-1) as e:
+        e.store_factors(True)
+        e.set_pivoting(0)
+        e.init_matrix_spd(42)
+        e.factor()
+        Fsim = e.get_F_global()
+    assert np.array_equal(Fsim, F), "sim and distributed factors must be bit-identical"
 
 
 def test_bench_dist_launch(tmp_path):
