@@ -88,6 +88,19 @@ def _load():
     lib.conflux_lu_debug_residual_dd_bench.argtypes = [
         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
         ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
+    lib.conflux_lu_solve_trans.argtypes = lib.conflux_lu_solve.argtypes
+    lib.conflux_lu_rcond.argtypes = [
+        ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int),
+        ctypes.POINTER(ctypes.c_double)]
+    lib.conflux_chol_rcond.argtypes = [
+        ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
+        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int),
+        ctypes.POINTER(ctypes.c_double)]
+    lib.conflux_lu_debug_trsm_left_trans.argtypes = \
+        lib.conflux_lu_debug_trsm_left.argtypes
+    lib.conflux_lu_debug_update_skinny_t.argtypes = \
+        lib.conflux_lu_debug_update_skinny.argtypes
     return lib
 
 
@@ -230,6 +243,47 @@ class Engine:
         (same conventions as solve)."""
         return self._solve(lib().conflux_chol_solve, "solve_cholesky", B,
                            return_ms)
+
+    def solve_transposed(self, B, return_ms=False):
+        """Solve A^T X = B with the stored factors of the last factor()
+        (conflux_lu_solve_trans; same conventions as solve).  Raises
+        ConfluxLuError after factor_cholesky(): there A = A^T and
+        solve_cholesky is the answer."""
+        return self._solve(lib().conflux_lu_solve_trans, "solve_transposed",
+                           B, return_ms)
+
+    def _rcond(self, what, call, return_info):
+        rc = ctypes.c_double()
+        an = ctypes.c_double()
+        ns = ctypes.c_int()
+        ms = ctypes.c_double()
+        _chk(call(ctypes.byref(rc), ctypes.byref(an), ctypes.byref(ns),
+                  ctypes.byref(ms)), what)
+        if not return_info:
+            return rc.value
+        return rc.value, dict(anorm=an.value, nsolves=ns.value, ms=ms.value)
+
+    def rcond(self, norm="1", return_info=False):
+        """Estimate 1 / (||A|| ||A^-1||) of the (padded) matrix of the last
+        factor() in the 1-norm (norm="1") or the infinity norm (norm="I")
+        (conflux_lu_rcond: exact ||A||, Higham's estimator for ||A^-1||, so
+        the result is an upper bound on the true rcond, usually tight).  0.0
+        for a singular factorization.  return_info=True returns
+        (rcond, info), info = dict(anorm=||A||, nsolves=single-RHS solves
+        used, ms=device time of the estimation loop)."""
+        if norm not in ("1", "I"):
+            raise ValueError(f'rcond: norm must be "1" or "I", got {norm!r}')
+        n = 0 if norm == "1" else 1
+        return self._rcond(
+            "rcond", lambda *a: lib().conflux_lu_rcond(self._h, n, *a),
+            return_info)
+
+    def rcond_cholesky(self, return_info=False):
+        """rcond for the matrix of the last factor_cholesky() (symmetric:
+        the two norms coincide).  Both triangles of the input must hold A."""
+        return self._rcond(
+            "rcond_cholesky",
+            lambda *a: lib().conflux_chol_rcond(self._h, *a), return_info)
 
     def _solve_refined(self, fn, what, B, max_iter, return_info):
         import numpy as np

@@ -33,6 +33,7 @@
 
 #include "../../include/conflux_lu.h"
 #include "kernels.hpp"
+#include "norm1est.hpp"
 
 #define HIPCHK(x)                                                       \
     do {                                                                \
@@ -115,6 +116,7 @@ struct Ctx {
                                  // 1 = LU, 2 = Cholesky
     double anorm_inf = -1;       // ||A11in||inf for the refined solves; < 0 =
                                  // not computed since the last factorization
+    double anorm_one = -1;       // ||A11in||1 for the condition estimate, same
     int pivoting = 1;            // 1 = tournament (reference), 0 = none
                                  // (EmptyPivot fast path)
     bool have_comm = false;
@@ -2182,6 +2184,7 @@ static int snapshot_or_restore(conflux_lu_ctx *c) {
     HIPCHK(hipStreamSynchronize(c->stream));
     c->input_dirty = false;
     c->anorm_inf = -1;
+    c->anorm_one = -1;
     return CONFLUX_LU_OK;
 }
 
@@ -2489,8 +2492,9 @@ static int assemble_global(conflux_lu_ctx *c, double *G, Pick which) {
     return CONFLUX_LU_OK;
 }
 
-// The guards every solve entry point shares.
-static int solve_guard(conflux_lu_ctx *c, bool chol, const double *B,
+// The guards every solve entry point shares (the condition estimates have
+// no B: they pass their own output pointer and nrhs = 1).
+static int solve_guard(conflux_lu_ctx *c, bool chol, const void *B,
                        int nrhs) {
     if (!c || !B || nrhs <= 0) return CONFLUX_LU_EARG;
     if (c->factored_kind != (chol ? 2 : 1)) return CONFLUX_LU_EARG;
@@ -2541,8 +2545,17 @@ static int solve_permute(conflux_lu_ctx *c, bool chol, const SolveDev &sd,
 }
 
 // The two sweeps, in place on the device buffer Xd (N x nrhs, ld = nrhs).
+// Both directions walk the same sb-blocks of the same F and differ in what
+// they launch per block:
+//   plain  forward  L_kk^-1 (unit for LU),  X[k+1:] -= F[k+1:, k] X_k
+//          backward U_kk^-1,                X[:k]   -= F[:k, k]   X_k
+//   trans  forward  U_kk^-T,                X[k+1:] -= F[k, k+1:]^T X_k
+//          backward L_kk^-T (unit),         X[:k]   -= F[k, :k]^T   X_k
+// (A^T = U^T L^T P; LU only).  The transposed update reads a ROW panel of F
+// in place through k_update_skinny_t for every nrhs — there is no transposed
+// GEMM to switch to, so CONFLUX_SOLVE_SKINNY does not apply to it.
 static void solve_sweeps(conflux_lu_ctx *c, bool chol, const SolveDev &sd,
-                         double *Xd, int nrhs) {
+                         double *Xd, int nrhs, bool trans = false) {
     const int64_t N = c->N;
     const int v = c->v;
     const double *Fg = sd.Fg;
@@ -2552,32 +2565,44 @@ static void solve_sweeps(conflux_lu_ctx *c, bool chol, const SolveDev &sd,
     const int nb = (int)(N / sb);
     auto update = [&](const double *A, const double *Xk, double *C, int M) {
         if (M <= 0) return;
-        if (skinny)
+        if (trans)
+            launch_update_skinny_t(A, ldf, Xk, nrhs, C, nrhs, M, nrhs, sb,
+                                   c->stream);
+        else if (skinny)
             launch_update_skinny(A, ldf, Xk, nrhs, C, nrhs, M, nrhs, sb,
                                  c->stream);
         else
             launch_dgemm_f64(A, ldf, Xk, nrhs, C, nrhs, M, nrhs, sb,
                              c->stream);
     };
-    for (int k = 0; k < nb; ++k) {  // forward: L (unit for LU)
+    // diagonal block solve: plain takes the lower half first, trans the upper
+    auto tri = [&](int64_t o, double *Xk, int upper_stored, int unit) {
+        if (trans)
+            launch_trsm_left_tri_mfma_t(Fg + o * ldf + o, ldf, Xk, nrhs, sb,
+                                        nrhs, upper_stored, unit, c->stream);
+        else
+            launch_trsm_left_tri_mfma(Fg + o * ldf + o, ldf, Xk, nrhs, sb,
+                                      nrhs, upper_stored, unit, c->stream);
+    };
+    for (int k = 0; k < nb; ++k) {  // forward: L (unit for LU) / U^T
         const int64_t o = i64(k) * sb;
         double *Xk = Xd + o * nrhs;
-        launch_trsm_left_tri_mfma(Fg + o * ldf + o, ldf, Xk, nrhs, sb, nrhs, 0,
-                                  chol ? 0 : 1, c->stream);
-        update(Fg + (o + sb) * ldf + o, Xk, Xk + i64(sb) * nrhs,
-               (int)(N - o - sb));
+        tri(o, Xk, trans ? 1 : 0, (trans || chol) ? 0 : 1);
+        update(trans ? Fg + o * ldf + o + sb : Fg + (o + sb) * ldf + o, Xk,
+               Xk + i64(sb) * nrhs, (int)(N - o - sb));
     }
     for (int k = nb - 1; k >= 0; --k) {  // backward: U (or L^T, mirrored up)
-        const int64_t o = i64(k) * sb;
+        const int64_t o = i64(k) * sb;   //           / L^T (unit)
         double *Xk = Xd + o * nrhs;
-        launch_trsm_left_tri_mfma(Fg + o * ldf + o, ldf, Xk, nrhs, sb, nrhs, 1,
-                                  0, c->stream);
-        update(Fg + o, Xk, Xd, (int)o);
+        tri(o, Xk, trans ? 0 : 1, trans ? 1 : 0);
+        update(trans ? Fg + o * ldf : Fg + o, Xk, Xd, (int)o);
     }
 }
 
+// trans (LU only): A^T X = B.  The sweeps run on B as uploaded and the
+// permutation comes last, as a scatter: P x = z, X[perm[r]] = Z[r].
 static int solve_common(conflux_lu_ctx *c, bool chol, double *B, int nrhs,
-                        double *elapsed_ms) {
+                        double *elapsed_ms, bool trans = false) {
     if (int rc = solve_guard(c, chol, B, nrhs)) return rc;
     const int64_t N = c->N;
 
@@ -2601,25 +2626,29 @@ static int solve_common(conflux_lu_ctx *c, bool chol, double *B, int nrhs,
         return rc;
     }
     SCHK(hipMalloc(&Xd, N * nrhs * 8));
-    if (chol) {
+    if (chol || trans) {
         SCHK(hipMemcpyAsync(Xd, B, N * nrhs * 8, hipMemcpyHostToDevice,
                             c->stream));
+        if (trans) SCHK(hipMalloc(&Bd, N * nrhs * 8));
     } else {
         SCHK(hipMalloc(&Bd, N * nrhs * 8));
         SCHK(hipMemcpyAsync(Bd, B, N * nrhs * 8, hipMemcpyHostToDevice,
                             c->stream));
     }
-    if (solve_permute(c, chol, sd, chol ? Xd : Bd, Xd, nrhs)) {
+    if (!trans && solve_permute(c, chol, sd, chol ? Xd : Bd, Xd, nrhs)) {
         cleanup();
         return CONFLUX_LU_EHIP;
     }
     SCHK(hipEventCreate(&e0));
     SCHK(hipEventCreate(&e1));
     SCHK(hipEventRecord(e0, c->stream));
-    solve_sweeps(c, chol, sd, Xd, nrhs);
+    solve_sweeps(c, chol, sd, Xd, nrhs, trans);
     SCHK(hipEventRecord(e1, c->stream));
-    SCHK(hipMemcpyAsync(B, Xd, N * nrhs * 8, hipMemcpyDeviceToHost,
-                        c->stream));
+    if (trans)
+        launch_row_scatter(Xd, nrhs, Bd, nrhs, sd.d_pm, (int)N, nrhs,
+                           c->stream);
+    SCHK(hipMemcpyAsync(B, trans ? Bd : Xd, N * nrhs * 8,
+                        hipMemcpyDeviceToHost, c->stream));
     SCHK(hipStreamSynchronize(c->stream));
     SCHK(hipGetLastError());
     if (elapsed_ms) {
@@ -2640,6 +2669,152 @@ int conflux_lu_solve(conflux_lu_ctx *c, double *B, int nrhs,
 int conflux_chol_solve(conflux_lu_ctx *c, double *B, int nrhs,
                        double *elapsed_ms) {
     return solve_common(c, true, B, nrhs, elapsed_ms);
+}
+
+/* A^T X = B on the stored LU factors (getrs with trans = 'T').  EARG after a
+ * Cholesky run through the shared guard: there A = A^T and
+ * conflux_chol_solve is the answer. */
+int conflux_lu_solve_trans(conflux_lu_ctx *c, double *B, int nrhs,
+                           double *elapsed_ms) {
+    return solve_common(c, false, B, nrhs, elapsed_ms, true);
+}
+
+/* Reciprocal condition number 1 / (||A|| ||A^-1||) of the matrix last
+ * factored (gecon / pocon): ||A|| from the input snapshot, ||A^-1||
+ * estimated by norm1est.hpp from single-RHS solves with A and A^T on the
+ * stored factors.  The solves run on device; the estimator's O(N) steps run
+ * on the host between them in a fixed order (one N-double upload and
+ * download per solve), so two calls agree bitwise.  F and perm are staged
+ * once per call.  ||A||1 (k_col_abs_sums) and ||A||inf (k_row_abs_sums) are
+ * computed on first use and cached until the next factorization; the
+ * snapshot is read in place on a Px = Py = 1 grid, else assembled into one
+ * N^2 staging copy that is freed before the solves start.
+ * inf-norm: ||A^-1||inf = ||A^-T||1, so the two callbacks swap roles.
+ * Cholesky: A = A^T, both callbacks are conflux_chol_solve's sweeps. */
+static int rcond_common(conflux_lu_ctx *c, bool chol, int norm, double *rcond,
+                        double *anorm_out, int *nsolves, double *elapsed_ms) {
+    if (int rc = solve_guard(c, chol, rcond, 1)) return rc;
+    if (norm != 0 && norm != 1) return CONFLUX_LU_EARG;
+    const int64_t N = c->N;
+    RankState *r00 = c->sim ? get_rs(*c, 0, 0, 0) : &c->rs[0];
+    if (!r00->A11in) return CONFLUX_LU_EARG;
+    const bool aliasA = c->Px == 1 && c->Py == 1;
+
+    SolveDev sd;
+    double *Ag = nullptr, *Xd = nullptr, *Bd = nullptr, *d_sums = nullptr,
+           *d_sc = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto cleanup = [&]() {
+        sd.release();
+        if (Ag && !aliasA) (void)hipFree(Ag);
+        for (double *p : {Xd, Bd, d_sums, d_sc})
+            if (p) (void)hipFree(p);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    };
+#define SCHK(x)                                                               \
+    if ((x) != hipSuccess) {                                                  \
+        cleanup();                                                            \
+        return CONFLUX_LU_EHIP;                                               \
+    }
+    double &cached = norm == 0 ? c->anorm_one : c->anorm_inf;
+    if (cached < 0) {  // once per factorization and norm
+        int64_t lda = N;
+        if (aliasA) {
+            Ag = r00->A11in;
+            lda = c->Nl;
+        } else {
+            SCHK(hipMalloc(&Ag, N * N * 8));
+            if (int rc = assemble_global(
+                    c, Ag, [](const RankState &r) { return r.A11in; })) {
+                cleanup();
+                return rc;
+            }
+        }
+        SCHK(hipMalloc(&d_sums, (size_t)N * 8));
+        SCHK(hipMalloc(&d_sc, 8));
+        if (norm == 0)
+            launch_col_abs_sums(Ag, lda, (int)N, (int)N, d_sums, c->stream);
+        else
+            launch_row_abs_sums(Ag, lda, (int)N, (int)N, d_sums, c->stream);
+        launch_colmax_abs(d_sums, N, 1, d_sc, c->stream);
+        double nrm = 0;
+        SCHK(hipMemcpyAsync(&nrm, d_sc, 8, hipMemcpyDeviceToHost, c->stream));
+        SCHK(hipStreamSynchronize(c->stream));
+        cached = nrm;
+        if (!aliasA) {
+            (void)hipFree(Ag);
+            Ag = nullptr;
+        }
+    }
+    const double anorm = cached;
+
+    if (int rc = solve_stage(c, chol, sd)) {
+        cleanup();
+        return rc;
+    }
+    SCHK(hipMalloc(&Xd, (size_t)N * 8));
+    if (!chol) SCHK(hipMalloc(&Bd, (size_t)N * 8));
+    hipError_t herr = hipSuccess;  // the callbacks cannot return: first error
+    auto up = [&](double *dst, const double *x) {
+        if (herr == hipSuccess)
+            herr = hipMemcpyAsync(dst, x, (size_t)N * 8,
+                                  hipMemcpyHostToDevice, c->stream);
+    };
+    auto down = [&](double *x, const double *src) {
+        if (herr == hipSuccess)
+            herr = hipMemcpyAsync(x, src, (size_t)N * 8,
+                                  hipMemcpyDeviceToHost, c->stream);
+        if (herr == hipSuccess) herr = hipStreamSynchronize(c->stream);
+    };
+    auto apply = [&](double *x) {  // x <- A^-1 x
+        up(chol ? Xd : Bd, x);
+        if (herr == hipSuccess && solve_permute(c, chol, sd, chol ? Xd : Bd,
+                                                Xd, 1))
+            herr = hipErrorUnknown;
+        if (herr == hipSuccess) solve_sweeps(c, chol, sd, Xd, 1);
+        down(x, Xd);
+    };
+    auto apply_t = [&](double *x) {  // x <- A^-T x
+        if (chol) return apply(x);
+        up(Xd, x);
+        if (herr == hipSuccess) {
+            solve_sweeps(c, false, sd, Xd, 1, true);
+            launch_row_scatter(Xd, 1, Bd, 1, sd.d_pm, (int)N, 1, c->stream);
+        }
+        down(x, Bd);
+    };
+    SCHK(hipEventCreate(&e0));
+    SCHK(hipEventCreate(&e1));
+    SCHK(hipEventRecord(e0, c->stream));
+    const norm1est::Result est =
+        norm == 0 ? norm1est::estimate((int)N, apply, apply_t)
+                  : norm1est::estimate((int)N, apply_t, apply);
+    SCHK(herr);
+    SCHK(hipEventRecord(e1, c->stream));
+    SCHK(hipStreamSynchronize(c->stream));
+    SCHK(hipGetLastError());
+    *rcond = norm1est::rcond_from(anorm, est.est);
+    if (anorm_out) *anorm_out = anorm;
+    if (nsolves) *nsolves = est.nsolves;
+    if (elapsed_ms) {
+        float ms = 0;
+        SCHK(hipEventElapsedTime(&ms, e0, e1));
+        *elapsed_ms = ms;
+    }
+#undef SCHK
+    cleanup();
+    return CONFLUX_LU_OK;
+}
+
+int conflux_lu_rcond(conflux_lu_ctx *c, int norm, double *rcond,
+                     double *anorm, int *nsolves, double *elapsed_ms) {
+    return rcond_common(c, false, norm, rcond, anorm, nsolves, elapsed_ms);
+}
+
+int conflux_chol_rcond(conflux_lu_ctx *c, double *rcond, double *anorm,
+                       int *nsolves, double *elapsed_ms) {
+    return rcond_common(c, true, 0, rcond, anorm, nsolves, elapsed_ms);
 }
 
 /* Solve with extra-precise iterative refinement (the xGERFSX idea: the
@@ -3090,6 +3265,69 @@ int conflux_lu_debug_update_skinny(int M, int nrhs, int K, int64_t lda,
         e = hipMemcpy(dC, C, i64(M) * nrhs * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         launch_update_skinny(dA, lda, dB, nrhs, dC, nrhs, M, nrhs, K, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess)
+        e = hipMemcpy(C, dC, i64(M) * nrhs * 8, hipMemcpyDeviceToHost);
+    cleanup();
+    HIPCHK(e);
+    return CONFLUX_LU_OK;
+}
+
+// X (v x N) <- T^-T X with T (v x ldt host, only its stored triangle read)
+int conflux_lu_debug_trsm_left_trans(int upper_stored, int unit, int v,
+                                     int64_t N, int64_t ldt, const double *T,
+                                     double *X) {
+    if (v <= 0 || N <= 0 || ldt < v || !T || !X) return CONFLUX_LU_EARG;
+    double *dT = nullptr, *dX = nullptr;
+    auto cleanup = [&]() {
+        for (double *p : {dT, dX})
+            if (p) (void)hipFree(p);
+    };
+    hipError_t e = hipMalloc(&dT, i64(v) * ldt * 8);
+    if (e == hipSuccess) e = hipMalloc(&dX, i64(v) * N * 8);
+    if (e == hipSuccess)
+        e = hipMemcpy(dT, T, i64(v) * ldt * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMemcpy(dX, X, i64(v) * N * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_trsm_left_tri_mfma_t(dT, ldt, dX, N, v, N, upper_stored, unit,
+                                    nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess)
+        e = hipMemcpy(X, dX, i64(v) * N * 8, hipMemcpyDeviceToHost);
+    cleanup();
+    HIPCHK(e);
+    return CONFLUX_LU_OK;
+}
+
+// C (M x nrhs) -= A^T B, A (K x lda host, M columns used), B (K x nrhs)
+int conflux_lu_debug_update_skinny_t(int M, int nrhs, int K, int64_t lda,
+                                     const double *A, const double *B,
+                                     double *C) {
+    if (M <= 0 || nrhs <= 0 || nrhs > 16 || K <= 0 || lda < M || !A || !B ||
+        !C)
+        return CONFLUX_LU_EARG;
+    double *dA = nullptr, *dB = nullptr, *dC = nullptr;
+    auto cleanup = [&]() {
+        for (double *p : {dA, dB, dC})
+            if (p) (void)hipFree(p);
+    };
+    hipError_t e = hipMalloc(&dA, i64(K) * lda * 8);
+    if (e == hipSuccess) e = hipMalloc(&dB, i64(K) * nrhs * 8);
+    if (e == hipSuccess) e = hipMalloc(&dC, i64(M) * nrhs * 8);
+    if (e == hipSuccess)
+        e = hipMemcpy(dA, A, i64(K) * lda * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMemcpy(dB, B, i64(K) * nrhs * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMemcpy(dC, C, i64(M) * nrhs * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_update_skinny_t(dA, lda, dB, nrhs, dC, nrhs, M, nrhs, K,
+                               nullptr);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();

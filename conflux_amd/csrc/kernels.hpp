@@ -53,6 +53,18 @@ void launch_trsm_left_tri_mfma(const double *T, int64_t ldt, double *X,
 void launch_update_skinny(const double *A, int64_t lda, const double *B,
                           int64_t ldb, double *C, int64_t ldc, int M, int nrhs,
                           int K, hipStream_t s);
+// solve_kernels.hip, transposed solve: X (v x N) <- T^-T X on the same stored
+// triangle (upper_stored names the half of T that holds it); C (M x nrhs) -=
+// A^T B with A stored K x M (a row panel of F), any nrhs (16-column groups);
+// out[col] = sum_i |A[i][col]|
+void launch_trsm_left_tri_mfma_t(const double *T, int64_t ldt, double *X,
+                                 int64_t ldx, int v, int64_t N,
+                                 int upper_stored, int unit, hipStream_t s);
+void launch_update_skinny_t(const double *A, int64_t lda, const double *B,
+                            int64_t ldb, double *C, int64_t ldc, int M,
+                            int nrhs, int K, hipStream_t s);
+void launch_col_abs_sums(const double *A, int64_t lda, int M, int K,
+                         double *out, hipStream_t s);
 // solve_kernels.hip, refinement: R (M x nrhs) = B - A X in doubled precision
 // (ld of X, B, R = nrhs; R must not alias B or X), in passes of
 // conflux_residual_group_width() columns; out[row] = sum_k |A[row][k]|;

@@ -10,6 +10,14 @@
 //                         the tall rank-v update of a sweep, bandwidth-bound
 //                         (each element of F is read once per sweep).
 //
+// of the transposed solve (conflux_lu_solve_trans, A^T X = B on the same
+// factors, read in place — no transposed copy of F):
+//
+//   k_trsm_left_tri_mfma<.., TRANS>   X <- T^-T X on the stored T.
+//   k_update_skinny_t     C (M x nc) -= A^T B, A a K x M row panel of F,
+//                         nc <= 16; the launcher loops over 16-column groups.
+//   k_col_abs_sums        ||A||1 for the condition estimate.
+//
 // and of the refined solves (conflux_lu_solve_refined /
 // conflux_chol_solve_refined), which the reference has no counterpart of
 // either:
@@ -46,9 +54,16 @@ namespace ck {
 // It is identity-padded in LDS (diagonal 1, off-diagonal 0, X rows 0); the
 // padding is never stored.  The half of T on the other side of the diagonal
 // (and the diagonal itself when UNIT) is never read.
+//
+// TRANS solves T^T X = B on the same stored T: S = T^T is the opposite
+// triangle, so the sweep runs in the opposite direction (SUP below).  The
+// 32x32 blocks of T are still loaded along their STORED rows (coalesced) and
+// transposed on the way into LDS (sT's rows are padded to 33 doubles, so the
+// transposed writes spread over the banks); everything downstream of LDS is
+// unchanged.
 // ---------------------------------------------------------------------------
 #define TRI_COLS 128
-template <bool UPPER, bool UNIT>
+template <bool UPPER, bool UNIT, bool TRANS = false>
 __global__ __launch_bounds__(256) void k_trsm_left_tri_mfma(
     const double *__restrict__ T, int64_t ldt, double *__restrict__ X,
     int64_t ldx, int v, int64_t N) {
@@ -61,12 +76,16 @@ __global__ __launch_bounds__(256) void k_trsm_left_tri_mfma(
     const int64_t c0 = (int64_t)blockIdx.x * TRI_COLS;
     const int cols = (int)min((int64_t)TRI_COLS, N - c0);
     const int nblk = (v + 31) / 32;
+    constexpr bool SUP = UPPER != TRANS;  // the triangle of the solved system
     double rx[16], rt[4];  // 32x128 X panel + 32x32 T block per iteration
+    // block (rows jb.., columns pb..) of the solved system; TRANS: that is
+    // stored block (rows pb.., columns jb..), read along its stored rows
     auto load_t_regs = [&](int pb, int jb) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int e = tid + i * 256;
-            const int gr = jb + (e >> 5), gc = pb + (e & 31);
+            const int gr = (TRANS ? pb : jb) + (e >> 5);
+            const int gc = (TRANS ? jb : pb) + (e & 31);
             rt[i] = (gr < v && gc < v) ? T[(int64_t)gr * ldt + gc] : 0.0;
         }
     };
@@ -88,13 +107,16 @@ __global__ __launch_bounds__(256) void k_trsm_left_tri_mfma(
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int e = tid + i * 256;
-            sT[buf][e >> 5][e & 31] = rt[i];
+            if (TRANS)
+                sT[buf][e & 31][e >> 5] = rt[i];
+            else
+                sT[buf][e >> 5][e & 31] = rt[i];
         }
     };
     for (int it = 0; it < nblk; ++it) {
-        const int jb = (UPPER ? nblk - 1 - it : it) * 32;
+        const int jb = (SUP ? nblk - 1 - it : it) * 32;
         // solved panels so far: `it` of them, below (lower) / above (upper)
-        auto pb_of = [&](int i) { return UPPER ? jb + 32 * (i + 1) : 32 * i; };
+        auto pb_of = [&](int i) { return SUP ? jb + 32 * (i + 1) : 32 * i; };
         __syncthreads();
         for (int i = tid; i < 32 * TRI_COLS; i += 256) {
             const int gr = jb + (i >> 7), cc = i & (TRI_COLS - 1);
@@ -145,15 +167,17 @@ __global__ __launch_bounds__(256) void k_trsm_left_tri_mfma(
         }
         // diagonal block, masked to its triangle and identity-padded
         for (int i = tid; i < 32 * 32; i += 256) {
-            const int r = i >> 5, c = i & 31;
+            // (r, c) in the solved system; TRANS walks c slowest so that
+            // consecutive threads still read one stored row of T
+            const int r = TRANS ? i & 31 : i >> 5, c = TRANS ? i >> 5 : i & 31;
             const int gr = jb + r, gc = jb + c;
+            const int64_t at =
+                TRANS ? (int64_t)gc * ldt + gr : (int64_t)gr * ldt + gc;
             double t;
             if (r == c)
-                t = (UNIT || gr >= v) ? 1.0 : T[(int64_t)gr * ldt + gc];
+                t = (UNIT || gr >= v) ? 1.0 : T[at];
             else
-                t = ((UPPER ? c > r : c < r) && gr < v && gc < v)
-                        ? T[(int64_t)gr * ldt + gc]
-                        : 0.0;
+                t = ((SUP ? c > r : c < r) && gr < v && gc < v) ? T[at] : 0.0;
             sT[0][r][c] = t;
         }
         __syncthreads();
@@ -161,7 +185,7 @@ __global__ __launch_bounds__(256) void k_trsm_left_tri_mfma(
             double x[32];
 #pragma unroll
             for (int r = 0; r < 32; ++r) x[r] = sXj[r][tid];
-            if (UPPER) {
+            if (SUP) {
 #pragma unroll
                 for (int k = 31; k >= 0; --k) {
                     if (!UNIT) x[k] /= sT[0][k][k];
@@ -271,6 +295,91 @@ __global__ __launch_bounds__(256) void k_update_skinny(
         }
         // f64 16x16x4 C/D map: lane l, reg q -> D[4*q + (l >> 4)][l & 15]
         if (frow < nrhs) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int r = t * 16 + 4 * q + fk;
+                if (r < M) C[(int64_t)r * ldc + frow] -= acc[q];
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Transposed skinny update C (M x nc) -= A^T B with A stored K x M — a ROW
+// panel of F (lda = ldf), the update of the A^T X = B sweeps — B (K x nc),
+// 1 <= nc <= 16, K <= SKN_KMAX per launch.  Same tiling as k_update_skinny:
+// one 16x16 MFMA tile per wave, B staged (zero-padded to 16 columns) in LDS
+// once per block, waves grid-stride over 16-row tiles of C, one owner each.
+// The MFMA A operand [row i][k] is F[k][i], so here the lanes walk ACROSS the
+// stored row: lane (i = l & 15, fk = l >> 4) loads A[k][16 t + i] for
+// k = 4 kk + fk — the 16 lanes of a k read 128 contiguous bytes of one stored
+// row, a wave 4 such rows per load.  Any k order serves the global loads
+// equally, so the steps use k_update_skinny's: step (u, s) of a group takes
+// k = g*64 + u*16 + fk*4 + s for both operands, which keeps the sB reads of
+// the four fk groups 4 rows (32 banks) apart.  Loads run one 64-deep k group
+// (16 per lane) ahead of the MFMAs in a second register buffer.
+// FULL: K % 64 == 0, no k bound checks.  Columns past M re-read column M-1
+// (in bounds); their results are dropped.  Rows k >= K are never read.
+// The compiler's resource usage (-Rpass-analysis=kernel-resource-usage),
+// FULL / not: 248 / 250 VGPRs, 2 / 1 waves per SIMD, no spill, no scratch.
+// The 80 KiB of sB cap a CU at two blocks (2 waves per SIMD) anyway, as for
+// k_update_skinny, so FULL — what the sweeps launch whenever 64 | sb — loses
+// nothing to its registers.
+// ---------------------------------------------------------------------------
+template <bool FULL>
+__global__ __launch_bounds__(256) void k_update_skinny_t(
+    const double *__restrict__ A, int64_t lda, const double *__restrict__ B,
+    int64_t ldb, double *__restrict__ C, int64_t ldc, int M, int nc, int K) {
+    __shared__ double sB[SKN_KMAX][SKN_RS];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int frow = lane & 15, fk = lane >> 4;
+    const int ngrp = (K + 63) / 64;
+    for (int i = tid; i < ngrp * 64 * 16; i += 256) {
+        const int k = i >> 4, c = i & 15;
+        sB[k][c] = (k < K && c < nc) ? B[(int64_t)k * ldb + c] : 0.0;
+    }
+    __syncthreads();
+    const int ntiles = (M + 15) / 16;
+    for (int t = blockIdx.x * 4 + wave; t < ntiles; t += gridDim.x * 4) {
+        const double *ap = A + min(t * 16 + frow, M - 1);
+        double ra[2][4][4];  // [buffer][chunk u][s]
+        auto load_group = [&](int g, int buf) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const int k = g * 64 + u * 16 + fk * 4 + s;
+                    ra[buf][u][s] =
+                        (FULL || k < K) ? ap[(int64_t)k * lda] : 0.0;
+                }
+        };
+        f64x4 acc = {0, 0, 0, 0};
+        load_group(0, 0);
+        for (int g = 0; g < ngrp; g += 2) {
+            // two groups per trip so the register buffers index statically
+            if (g + 1 < ngrp) load_group(g + 1, 1);
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+                    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(
+                        ra[0][u][s], sB[g * 64 + u * 16 + fk * 4 + s][frow],
+                        acc, 0, 0, 0);
+            if (g + 1 < ngrp) {
+                if (g + 2 < ngrp) load_group(g + 2, 0);
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+                        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(
+                            ra[1][u][s],
+                            sB[(g + 1) * 64 + u * 16 + fk * 4 + s][frow], acc,
+                            0, 0, 0);
+            }
+        }
+        // f64 16x16x4 C/D map: lane l, reg q -> D[4*q + (l >> 4)][l & 15]
+        if (frow < nc) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int r = t * 16 + 4 * q + fk;
@@ -425,6 +534,19 @@ __global__ __launch_bounds__(256) void k_row_abs_sums(
     if (lane == 0) out[row] = s;
 }
 
+// out[col] = sum_i |A[i][col]|: one thread per column walking the rows in
+// order (a row of threads reads a contiguous row segment), so the sum has one
+// fixed order.  max over the columns (k_colmax_abs) gives ||A||1.
+__global__ __launch_bounds__(64) void k_col_abs_sums(
+    const double *__restrict__ A, int64_t lda, int M, int K,
+    double *__restrict__ out) {
+    const int col = blockIdx.x * 64 + threadIdx.x;
+    if (col >= K) return;
+    double s = 0;
+    for (int i = 0; i < M; ++i) s += fabs(A[(int64_t)i * lda + col]);
+    out[col] = s;
+}
+
 // out[j] = max_i |V[i][j]| of an n x ncols array (ld = ncols): one block per
 // column.  A NaN in the column is returned, not skipped.
 __global__ __launch_bounds__(256) void k_colmax_abs(
@@ -476,6 +598,50 @@ void launch_trsm_left_tri_mfma(const double *T, int64_t ldt, double *X,
     else
         hipLaunchKernelGGL((k_trsm_left_tri_mfma<false, false>), grid, block,
                            0, s, T, ldt, X, ldx, v, N);
+}
+
+void launch_trsm_left_tri_mfma_t(const double *T, int64_t ldt, double *X,
+                                 int64_t ldx, int v, int64_t N,
+                                 int upper_stored, int unit, hipStream_t s) {
+    if (N <= 0 || v <= 0) return;
+    const dim3 grid((unsigned)((N + TRI_COLS - 1) / TRI_COLS)), block(256);
+    if (upper_stored && unit)
+        hipLaunchKernelGGL((k_trsm_left_tri_mfma<true, true, true>), grid,
+                           block, 0, s, T, ldt, X, ldx, v, N);
+    else if (upper_stored)
+        hipLaunchKernelGGL((k_trsm_left_tri_mfma<true, false, true>), grid,
+                           block, 0, s, T, ldt, X, ldx, v, N);
+    else if (unit)
+        hipLaunchKernelGGL((k_trsm_left_tri_mfma<false, true, true>), grid,
+                           block, 0, s, T, ldt, X, ldx, v, N);
+    else
+        hipLaunchKernelGGL((k_trsm_left_tri_mfma<false, false, true>), grid,
+                           block, 0, s, T, ldt, X, ldx, v, N);
+}
+
+void launch_update_skinny_t(const double *A, int64_t lda, const double *B,
+                            int64_t ldb, double *C, int64_t ldc, int M,
+                            int nrhs, int K, hipStream_t s) {
+    if (M <= 0 || nrhs <= 0 || K <= 0) return;
+    const int nblocks = std::min((M + 63) / 64, 2048);
+    // 16-column groups of B and C (each re-reads the panel); C -= is
+    // additive over K
+    for (int c0 = 0; c0 < nrhs; c0 += 16) {
+        const int nc = std::min(16, nrhs - c0);
+        for (int k0 = 0; k0 < K; k0 += SKN_KMAX) {
+            const int kc = std::min(SKN_KMAX, K - k0);
+            const double *a = A + (int64_t)k0 * lda;
+            const double *b = B + (int64_t)k0 * ldb + c0;
+            if (kc % 64 == 0)
+                hipLaunchKernelGGL(k_update_skinny_t<true>, dim3(nblocks),
+                                   dim3(256), 0, s, a, lda, b, ldb, C + c0,
+                                   ldc, M, nc, kc);
+            else
+                hipLaunchKernelGGL(k_update_skinny_t<false>, dim3(nblocks),
+                                   dim3(256), 0, s, a, lda, b, ldb, C + c0,
+                                   ldc, M, nc, kc);
+        }
+    }
 }
 
 void launch_update_skinny(const double *A, int64_t lda, const double *B,
@@ -548,6 +714,13 @@ void launch_row_abs_sums(const double *A, int64_t lda, int M, int K,
     if (M <= 0 || K <= 0) return;
     hipLaunchKernelGGL(k_row_abs_sums, dim3((unsigned)((M + 3) / 4)),
                        dim3(256), 0, s, A, lda, M, K, out);
+}
+
+void launch_col_abs_sums(const double *A, int64_t lda, int M, int K,
+                         double *out, hipStream_t s) {
+    if (M <= 0 || K <= 0) return;
+    hipLaunchKernelGGL(k_col_abs_sums, dim3((unsigned)((K + 63) / 64)),
+                       dim3(64), 0, s, A, lda, M, K, out);
 }
 
 void launch_colmax_abs(const double *V, int64_t n, int ncols, double *out,

@@ -15,6 +15,16 @@ evaluation R = B - A X, of one of its passes over A (a pass handles one
 column group) with the effective GB/s over N^2 * 8 B, next to a plain
 device-to-device copy of the same N^2 * 8 B in the same run.
 
+    python tools/solve_bench.py --trans [--rcond] [--N 16384] [--v 512]
+
+--trans benchmarks conflux_lu_solve_trans next to the plain solve: per nrhs
+the two alternate within one repetition loop (plain, transposed, plain, ...),
+and the medians, the ratio and both backward errors are printed.  --rcond
+adds (or, alone, runs only) the condition estimate: conflux_lu_rcond in both
+norms `--reps` times — rcond, ||A||, the solves taken, the median device ms
+of the estimation loop, and that time over nsolves x the nrhs = 1 plain
+solve of the same run.
+
 CONFLUX_SOLVE_SKINNY=0|1 (read once by the library) routes the nrhs <= 16
 update through the 128-wide GEMM (0) or the skinny kernel (1);
 CONFLUX_SOLVE_BLOCK=<divisor of v> sets the sweep block (default 128 for
@@ -92,20 +102,90 @@ def refine_main(a):
                               copy_ms=ms_c.value, copy_gbs_rw=cgbs)))
 
 
+def trans_rcond_main(a):
+    rng = np.random.default_rng(0)
+    nrhs_list = [int(x) for x in (a.nrhs or "1,16,128").split(",")]
+    with conflux_amd.Engine(a.N, a.v, 1, 1, 1, rank=-1) as e:
+        N = e.Npad
+        e.store_factors(True)
+        e.init_matrix(42)  # device-side fill == gen_matrix(N), seed 42
+        fms = e.factor()
+        print(f"N={N} v={a.v} factor {fms:.1f} ms")
+        A = None if a.no_verify else gen_matrix(N)
+        normA = None if A is None else np.linalg.norm(A)
+
+        def eta(M, X, B):
+            if M is None:
+                return float("nan")
+            return float(np.linalg.norm(B - M @ X) / (
+                normA * np.linalg.norm(X) + np.linalg.norm(B)))
+
+        if a.trans:
+            print(f"{'nrhs':>5} {'plain ms':>9} {'trans ms':>9} {'ratio':>6} "
+                  f"{'eta plain':>10} {'eta trans':>10}")
+            for nrhs in nrhs_list:
+                B = rng.standard_normal((N, nrhs))
+                e.solve(B)  # warm-up: code objects, allocator
+                e.solve_transposed(B)
+                tp, tt = [], []
+                for _ in range(a.reps):  # alternate within the run
+                    X, ms = e.solve(B, return_ms=True)
+                    tp.append(ms)
+                    Xt, ms = e.solve_transposed(B, return_ms=True)
+                    tt.append(ms)
+                mp, mt = statistics.median(tp), statistics.median(tt)
+                ep = eta(A, X, B)
+                et = eta(None if A is None else A.T, Xt, B)
+                print(f"{nrhs:>5} {mp:>9.3f} {mt:>9.3f} {mt / mp:>6.2f} "
+                      f"{ep:>10.2e} {et:>10.2e}")
+                print(json.dumps(dict(
+                    N=N, v=a.v, nrhs=nrhs, plain_ms_median=mp,
+                    trans_ms_median=mt, plain_ms_all=tp, trans_ms_all=tt,
+                    eta_plain=ep, eta_trans=et)))
+        if a.rcond:
+            b1 = rng.standard_normal(N)
+            e.solve(b1)
+            t1 = statistics.median(
+                e.solve(b1, return_ms=True)[1] for _ in range(a.reps))
+            print(f"{'norm':>5} {'rcond':>11} {'anorm':>11} {'nsolves':>7} "
+                  f"{'ms':>9} {'ms/(nsolves*solve)':>18}   "
+                  f"(nrhs=1 solve {t1:.3f} ms)")
+            for which in ("1", "I"):
+                e.rcond(which)  # warm-up; also caches ||A||
+                ts = []
+                for _ in range(a.reps):
+                    rc, info = e.rcond(which, return_info=True)
+                    ts.append(info["ms"])
+                med = statistics.median(ts)
+                over = med / (info["nsolves"] * t1)
+                print(f"{which:>5} {rc:>11.4e} {info['anorm']:>11.4e} "
+                      f"{info['nsolves']:>7} {med:>9.3f} {over:>18.2f}")
+                print(json.dumps(dict(
+                    N=N, v=a.v, norm=which, rcond=rc, anorm=info["anorm"],
+                    nsolves=info["nsolves"], ms_median=med, ms_all=ts,
+                    solve1_ms=t1, over_nsolves_x_solve=over)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--N", type=int, default=16384)
     ap.add_argument("--v", type=int, default=512)
     ap.add_argument("--nrhs", default=None,
-                    help="default 1,16,128,512 (--refine: 1,16,128)")
+                    help="default 1,16,128,512 (--refine, --trans: 1,16,128)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--refine", action="store_true",
                     help="benchmark the refined solve and its residual")
     ap.add_argument("--max-iter", type=int, default=10)
+    ap.add_argument("--trans", action="store_true",
+                    help="benchmark the transposed solve next to the plain")
+    ap.add_argument("--rcond", action="store_true",
+                    help="benchmark the condition estimate")
     a = ap.parse_args()
     if a.refine:
         return refine_main(a)
+    if a.trans or a.rcond:
+        return trans_rcond_main(a)
     a.nrhs = a.nrhs or "1,16,128,512"
     knob = os.environ.get("CONFLUX_SOLVE_SKINNY", "default")
     rng = np.random.default_rng(0)
