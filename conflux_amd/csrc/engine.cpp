@@ -360,11 +360,21 @@ int factor_panel(Ctx &c, RankState &r, int n, std::vector<int> &ipiv_out) {
         }
     }
     if (ev_end(c, slot)) return CONFLUX_LU_EHIP;
-    // fetch ipiv (+ overflow/err word of the sync struct)
+    // fetch ipiv + the err word of the sync struct (set by a key poll that
+    // gave up): same stream, one sync
     std::vector<int> raw(v);
+    unsigned int perr = 0;
+    char *d_err = (char *)r.sync + conflux_panel_err_offset();
     HIPCHK(hipMemcpyAsync(raw.data(), r.d_ipiv, nsteps * 4,
                           hipMemcpyDeviceToHost, c.stream));
+    HIPCHK(hipMemcpyAsync(&perr, d_err, 4, hipMemcpyDeviceToHost, c.stream));
     HIPCHK(hipStreamSynchronize(c.stream));
+    if (perr) {
+        HIPCHK(hipMemsetAsync(d_err, 0, 4, c.stream));
+        c.err = "panel hand-off timed out: column code " +
+                std::to_string(perr) + " (1 + sub-panel column)";
+        return CONFLUX_LU_EINTERNAL;
+    }
     for (int jb = 0; jb < nsteps; jb += NB) {
         const int nb = std::min(NB, nsteps - jb);
         for (int s = 0; s < nb; ++s) ipiv_out[jb + s] = jb + raw[jb + s];

@@ -231,12 +231,24 @@ __global__ void k_row_move(const double *__restrict__ src, int64_t lds,
 // reach c+2's publish before every block published c+1, so two slots
 // suffice).  Single-buffered slabs raced (old flag + new payload is
 // observable: no ordering between one block's reads and another's writes).
+//
+// The per-block key is SELF-VALIDATING (G16 R2, "the data IS the flag"): the
+// 64-bit pattern of the block's candidate |value| travels as two adjacent
+// 8-byte granules, each tagged with the full 32-bit epoch,
+//   key[par][b][0] = (epoch<<32) | hi32(bits),  key[par][b][1] = ... lo32,
+// so one poll pass (two independent loads = one fabric trip) returns the
+// value together with its validity and no dependent key read follows.  A
+// stale slot (taller earlier panel, tournament panel, earlier factorization)
+// carries an older epoch in BOTH granules and is rejected; the host's zero
+// memset stays valid because epoch >= 1.  The winner's ROW INDEX is payload:
+// it rides in a 17th 16-byte chunk of the block's candidate record.
+#define PANEL_REC (PANEL_NB + 2)  // doubles per candidate record (272 B)
 struct PanelSync2 {
-    unsigned long long key_abs[2][CONFLUX_PANEL_MAX_BLOCKS];
-    unsigned long long key_flag[2][CONFLUX_PANEL_MAX_BLOCKS];  // (epoch<<32)|row
-    double cand_row[2][CONFLUX_PANEL_MAX_BLOCKS][PANEL_NB];
-    double diag_row[2][PANEL_NB];
-    unsigned int diag_flag[2];
+    alignas(16) unsigned long long key[2][CONFLUX_PANEL_MAX_BLOCKS][2];
+    // candidate record: PANEL_NB row values, then one 16-byte chunk whose
+    // first int is the candidate's (sub-panel-relative) row index
+    alignas(16) double cand_row[2][CONFLUX_PANEL_MAX_BLOCKS][PANEL_REC];
+    alignas(16) double diag_row[2][PANEL_NB];
     unsigned int err;
     // diagnostics: total key-poll iterations (all blocks, all columns) —
     // read+reset by conflux_panel_spin_stats (CONFLUX_SPIN_STATS=1)
@@ -271,6 +283,38 @@ DEVFN double ld_rlx_f64(const double *p) {
     return x.d;
 }
 DEVFN void drain_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+// Wave64 first-max reduction of a (|value|, index) pair on the DPP network
+// (no LDS round trips): after wave_first_max() LANE 63 holds the pair with
+// the largest value, the smallest index among equal values.  The fold is
+// commutative and associative (values are never NaN here: a NaN never
+// becomes a candidate), so the order of the DPP stages does not matter.  A
+// lane whose DPP source is outside its row, or whose row is masked off,
+// keeps its own pair and folds it with itself (a no-op).  All 64 lanes must
+// be active.
+template <int CTRL, int ROW_MASK>
+DEVFN void dpp_fold_first_max(double &d, int &idx) {
+    union { double d; int i[2]; } s, o;
+    s.d = d;
+    o.i[0] = __builtin_amdgcn_update_dpp(s.i[0], s.i[0], CTRL, ROW_MASK, 0xf,
+                                         false);
+    o.i[1] = __builtin_amdgcn_update_dpp(s.i[1], s.i[1], CTRL, ROW_MASK, 0xf,
+                                         false);
+    const int oi =
+        __builtin_amdgcn_update_dpp(idx, idx, CTRL, ROW_MASK, 0xf, false);
+    if (o.d > d || (o.d == d && oi < idx)) {
+        d = o.d;
+        idx = oi;
+    }
+}
+DEVFN void wave_first_max(double &d, int &idx) {
+    dpp_fold_first_max<0x111, 0xf>(d, idx);  // row_shr:1
+    dpp_fold_first_max<0x112, 0xf>(d, idx);  // row_shr:2
+    dpp_fold_first_max<0x114, 0xf>(d, idx);  // row_shr:4
+    dpp_fold_first_max<0x118, 0xf>(d, idx);  // row_shr:8 -> lane 15 of a row
+    dpp_fold_first_max<0x142, 0xa>(d, idx);  // row_bcast:15 into rows 1, 3
+    dpp_fold_first_max<0x143, 0xc>(d, idx);  // row_bcast:31 into rows 2, 3
+}
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 union F64x2Bits {
@@ -333,7 +377,7 @@ __global__ __launch_bounds__(TPB) void k_panel_factor(
     __shared__ double diag_lds[PANEL_NB];
     __shared__ double red_abs[TPB];
     __shared__ int red_row[TPB];
-    __shared__ unsigned int sh_info[2];
+    __shared__ int sh_piv;  // winner's row, from the winner record
     // block 0 lane 0 composes the dlaswp row-permutation incrementally as
     // pivots are decided (replaces the separate k_swap_map launch):
     __shared__ int sm_base[PANEL_NB];
@@ -347,6 +391,20 @@ __global__ __launch_bounds__(TPB) void k_panel_factor(
         (void *)sync, (short)0, (int)sizeof(PanelSync2), 0x00020000);
 
     unsigned long long spin_acc = 0;  // key-poll iterations (diagnostics)
+    // give-up bound of the key poll: a broken hand-off must end the kernel
+    // in about two seconds (legitimate waits are well under a millisecond).
+    // One poll pass costs the two granule loads' round trip to L2 plus the
+    // backoff's s_sleep(k) = 64*k clocks ~= 27*k ns at 2.4 GHz.  The spin
+    // diagnostic gives the pass time: ~14.1 M passes per N=16384
+    // factorization over ~32 polling lanes x 16384 columns of ~7 us each
+    // is ~27 passes per column, ~0.26 us per pass at k = 2, so the load
+    // trip is ~200 ns:  passes = 2e9 ns / (200 + 27*k) ns  (~7.9 M at k=2;
+    // a loaded fabric lengthens a pass, and with it the bound, by 1.5-3x).
+    // factor_panel reads sync->err after every panel and reports the
+    // column code.
+    const unsigned sleep_k =
+        backoff == 1 ? 1u : backoff == 2 ? 2u : backoff >= 4 ? 4u : 0u;
+    const unsigned spin_limit = 2000000000u / (200u + 27u * sleep_k);
     for (int q = 0; q < QR; ++q) {
         const int r = r0 + q * TPB;
         for (int cc = 0; cc < nb; ++cc)
@@ -358,11 +416,26 @@ __global__ __launch_bounds__(TPB) void k_panel_factor(
     // buffer stores.  The owning (thread, q) of any row r is computable
     // from r directly (r = bid*RPB + tid + q*TPB), so the publishing lanes
     // read the owner's LDS slot; all publishing lanes are wave 0, one wave
-    // drain covers them, then lane 0 posts the key granule (R2: the flag
-    // carries the row) and — if this block owns row pc — the diag flag.
+    // drain covers them, then lane 0 posts the two key granules (R2: the
+    // granules carry the candidate |value| itself).  Lane 32 adds the
+    // candidate's row index as the record's 17th chunk.  There is no diag
+    // flag: the diagonal row pc is owned by block 0 (see the static_assert
+    // below), block 0 stores it before the same drain that precedes its key,
+    // and every block's lane 0 polls block 0's key — so the diag row is
+    // visible to a block once its key poll has passed.
+    static_assert(PANEL_NB <= RPB,
+                  "diag row pc < nb <= PANEL_NB must lie in block 0");
     auto publish_col = [&](int pc, double wa, int wrow) {
         const unsigned int pep = epoch0 + (unsigned)pc;
         const int ppar = (int)(pep & 1u);
+        const int rec_off =
+            (int)offsetof(PanelSync2, cand_row) +
+            (ppar * CONFLUX_PANEL_MAX_BLOCKS + bid) * PANEL_REC * 8;
+        if (tid == 32) {
+            i32x4 rv = {wrow, 0, 0, 0};
+            __builtin_amdgcn_raw_buffer_store_b128(
+                rv, srsrc, rec_off + PANEL_NB * 8, 0, /*sc1*/ 16);
+        }
         if (tid < 16) {
             const int lrow = (wrow < m) ? wrow - bid * RPB : 0;
             const int wq = lrow >= TPB;
@@ -372,12 +445,7 @@ __global__ __launch_bounds__(TPB) void k_panel_factor(
             x.d[1] = rows[wq][wtid][2 * tid + 1];
             if (2 * tid < nb)
                 __builtin_amdgcn_raw_buffer_store_b128(
-                    x.v, srsrc,
-                    (int)offsetof(PanelSync2, cand_row) +
-                        (ppar * CONFLUX_PANEL_MAX_BLOCKS + bid) * PANEL_NB *
-                            8 +
-                        16 * tid,
-                    0, /*sc1*/ 16);
+                    x.v, srsrc, rec_off + 16 * tid, 0, /*sc1*/ 16);
         } else if (tid < 32 && pc >= bid * RPB &&
                    pc < (bid + 1) * RPB) {
             const int l = tid - 16;
@@ -394,21 +462,17 @@ __global__ __launch_bounds__(TPB) void k_panel_factor(
                         ppar * PANEL_NB * 8 + 16 * l,
                     0, /*sc1*/ 16);
         }
-        // key_abs is payload like the slabs: store it BEFORE the joint
-        // drain so ONE vmcnt covers slabs + abs and the flag store follows
-        // immediately (one L2 round trip per column instead of two on the
-        // last publisher's critical path)
+        // ONE wave drain covers every payload store (all from wave 0), then
+        // lane 0 posts the key: the full bit pattern of wa (the -1.0 "no
+        // candidate" value and any NaN included), split over two granules
+        // that each carry the epoch
+        if (tid < 64) drain_stores();
         if (tid == 0) {
             union { double d; unsigned long long u; } a;
             a.d = wa;
-            st_rlx_u64(&sync->key_abs[ppar][bid], a.u);
-        }
-        if (tid < 64) drain_stores();
-        if (tid == 0) {
-            st_rlx_u64(&sync->key_flag[ppar][bid],
-                       ((unsigned long long)pep << 32) | (unsigned)wrow);
-            if (pc >= bid * RPB && pc < (bid + 1) * RPB)
-                st_rlx_u32(&sync->diag_flag[ppar], pep);
+            const unsigned long long tag = (unsigned long long)pep << 32;
+            st_rlx_u64(&sync->key[ppar][bid][0], tag | (a.u >> 32));
+            st_rlx_u64(&sync->key[ppar][bid][1], tag | (a.u & 0xffffffffull));
         }
     };
     // combine the four per-wave partials (redundantly on wave 0's lanes)
@@ -421,17 +485,10 @@ __global__ __launch_bounds__(TPB) void k_panel_factor(
             if (oa > wa || (oa == wa && orr < wrow)) { wa = oa; wrow = orr; }
         }
     };
-    // per-wave shuffle-tree + LDS partial write of a (|value|, row) pair
+    // per-wave DPP reduction + LDS partial write of a (|value|, row) pair
     auto reduce_to_partials = [&](double amax, int arow) {
-        for (int w = 32; w > 0; w >>= 1) {
-            const double oa = __shfl_down(amax, w);
-            const int orr = __shfl_down(arow, w);
-            if (oa > amax || (oa == amax && orr < arow)) {
-                amax = oa;
-                arow = orr;
-            }
-        }
-        if ((tid & 63) == 0) {
+        wave_first_max(amax, arow);
+        if ((tid & 63) == 63) {
             red_abs[tid >> 6] = amax;
             red_row[tid >> 6] = arow;
         }
@@ -467,59 +524,95 @@ __global__ __launch_bounds__(TPB) void k_panel_factor(
             (int)offsetof(PanelSync2, diag_row) + par * PANEL_NB * 8;
 
         // ---- EVERY block reduces the global winner itself (redundant,
-        // deterministic): lane b polls block b's flag granule, reads its
-        // |value|, shuffle-tree with the first-max rule.  Saves the central
-        // reducer's publish round trip.
+        // deterministic): lane b polls block b's two key granules until
+        // both carry this column's epoch, rebuilds the |value| from them,
+        // then one wave reduction with the first-max rule.  Saves the
+        // central reducer's publish round trip.  Per-column critical chain
+        // (three fabric trips): publisher's drain -> key granules visible
+        // to the poll -> winner record + diag row read.
+        //
+        // Tie-break: this RELIES on blocks owning contiguous ascending row
+        // ranges [bid*RPB, (bid+1)*RPB) (r0 = bid*RPB + tid, + q*TPB, for
+        // every QR/TPB shape) and on each block's candidate being its own
+        // first max: then "smaller row wins" between blocks is "smaller
+        // block index wins" — the row index is not needed for the
+        // reduction and arrives with the winner record.  A row-cyclic
+        // block layout would need the row back in the key.
         if (tid < 64) {
             double a_d = -1.0;
-            int a_row = m, a_win = 0;
+            int a_win = 0;
             for (int b = tid; b < nblocks; b += 64) {
-                unsigned long long g;
+                unsigned long long g0, g1;
                 unsigned spins = 0;
-                while (((g = ld_rlx_u64(&sync->key_flag[par][b])) >> 32) !=
-                       epoch) {
+                for (;;) {
+                    // two independent loads: one trip per pass
+                    g0 = ld_rlx_u64(&sync->key[par][b][0]);
+                    g1 = ld_rlx_u64(&sync->key[par][b][1]);
+                    if ((unsigned)(g0 >> 32) == epoch &&
+                        (unsigned)(g1 >> 32) == epoch)
+                        break;
                     if (backoff == 1) __builtin_amdgcn_s_sleep(1);
                     else if (backoff == 2) __builtin_amdgcn_s_sleep(2);
                     else if (backoff >= 4) __builtin_amdgcn_s_sleep(4);
-                    if (++spins > 800000000u) {
+                    if (++spins > spin_limit) {
                         st_rlx_u32(&sync->err, 1u + (unsigned)c);
                         break;
                     }
                 }
                 spin_acc += spins;
                 union { double d; unsigned long long u; } a;
-                a.u = ld_rlx_u64(&sync->key_abs[par][b]);
-                const int rr = (int)(g & 0xffffffffu);
-                if (a.d > a_d || (a.d == a_d && rr < a_row)) {
+                a.u = (g0 << 32) | (g1 & 0xffffffffull);
+                // b ascends per lane: strictly-greater keeps the lower block
+                if (a.d > a_d) {
                     a_d = a.d;
-                    a_row = rr;
                     a_win = b;
                 }
             }
-            for (int w = 32; w > 0; w >>= 1) {
-                const double od = __shfl_down(a_d, w);
-                const int orr = __shfl_down(a_row, w);
-                const int ow = __shfl_down(a_win, w);
-                if (od > a_d || (od == a_d && orr < a_row)) {
-                    a_d = od;
-                    a_row = orr;
-                    a_win = ow;
-                }
+            // lanes >= nblocks still hold the (-1.0, 0) start value, which
+            // never replaces a real candidate
+            wave_first_max(a_d, a_win);
+            // the polling wave is the loading wave: broadcast the winner and
+            // issue the payload loads at once (no LDS round + barrier in
+            // between).  The wavefront-scope fence emits no instruction; it
+            // keeps the compiler from moving the sc1 loads above the poll.
+            const int win = __builtin_amdgcn_readlane(a_win, 63);
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            i32x4 rec = {0, 0, 0, 0};
+            if (tid == 16 || (tid < 16 && 2 * tid < nb))
+                rec = __builtin_amdgcn_raw_buffer_load_b128(
+                    srsrc,
+                    (int)offsetof(PanelSync2, cand_row) +
+                        (par * CONFLUX_PANEL_MAX_BLOCKS + win) * PANEL_REC *
+                            8 +
+                        16 * tid,
+                    0, /*sc1*/ 16);
+            if (tid < 16 && 2 * tid < nb) {
+                F64x2Bits x;
+                x.v = rec;
+                piv_lds[2 * tid] = x.d[0];
+                piv_lds[2 * tid + 1] = x.d[1];
+                x.v = __builtin_amdgcn_raw_buffer_load_b128(
+                    srsrc, diag_off + 16 * tid, 0, /*sc1*/ 16);
+                diag_lds[2 * tid] = x.d[0];
+                diag_lds[2 * tid + 1] = x.d[1];
             }
+            // lane 16 holds the record's 17th chunk: the winner's row
+            const int w_row = __builtin_amdgcn_readlane(rec[0], 16);
             if (tid == 0) {
+                sh_piv = w_row;
                 if (bid == 0) {
-                    ipiv[c] = a_row;
-                    // compose the swap (c <-> a_row) into the row map
+                    ipiv[c] = w_row;
+                    // compose the swap (c <-> w_row) into the row map
                     int *b;
-                    if (a_row < nb) {
-                        b = &sm_base[a_row];
+                    if (w_row < nb) {
+                        b = &sm_base[w_row];
                     } else {
                         int j = 0;
-                        for (; j < sm_novf && sm_opos[j] != a_row; ++j) {
+                        for (; j < sm_novf && sm_opos[j] != w_row; ++j) {
                         }
                         if (j == sm_novf) {
-                            sm_opos[j] = a_row;
-                            sm_osrc[j] = a_row;
+                            sm_opos[j] = w_row;
+                            sm_osrc[j] = w_row;
                             ++sm_novf;
                         }
                         b = &sm_osrc[j];
@@ -528,38 +621,10 @@ __global__ __launch_bounds__(TPB) void k_panel_factor(
                     sm_base[c] = *b;
                     *b = t;
                 }
-                sh_info[0] = (unsigned)a_row;
-                sh_info[1] = (unsigned)a_win;
-                // wait the diagonal row publication too
-                unsigned spins = 0;
-                while (ld_rlx_u32(&sync->diag_flag[par]) != epoch) {
-                    __builtin_amdgcn_s_sleep(1);
-                    if (++spins > 800000000u) {
-                        st_rlx_u32(&sync->err, 1000000u + (unsigned)c);
-                        break;
-                    }
-                }
             }
         }
         __syncthreads();
-        const int piv = (int)sh_info[0];
-        const int win = (int)sh_info[1];
-        if (tid < 16 && 2 * tid < nb) {
-            F64x2Bits x;
-            x.v = __builtin_amdgcn_raw_buffer_load_b128(
-                srsrc,
-                (int)offsetof(PanelSync2, cand_row) +
-                    (par * CONFLUX_PANEL_MAX_BLOCKS + win) * PANEL_NB * 8 +
-                    16 * tid,
-                0, /*sc1*/ 16);
-            piv_lds[2 * tid] = x.d[0];
-            piv_lds[2 * tid + 1] = x.d[1];
-            x.v = __builtin_amdgcn_raw_buffer_load_b128(
-                srsrc, diag_off + 16 * tid, 0, /*sc1*/ 16);
-            diag_lds[2 * tid] = x.d[0];
-            diag_lds[2 * tid + 1] = x.d[1];
-        }
-        __syncthreads();
+        const int piv = sh_piv;
         const double pivval = piv_lds[c];
         const bool do_scale = pivval != 0.0;
         const double recip = do_scale ? 1.0 / pivval : 0.0;
@@ -1683,6 +1748,7 @@ void conflux_panel_spin_read(void *sync, unsigned long long *out,
 }
 
 int conflux_panel_sync_bytes() { return (int)sizeof(PanelSync2); }
+int conflux_panel_err_offset() { return (int)offsetof(PanelSync2, err); }
 int conflux_panel_nb() { return PANEL_NB; }
 int conflux_panel_rpb() {
     int qr, tpb;

@@ -29,6 +29,7 @@ int launch_panel_factor(double *panel, int64_t ldp, int m, int nb, void *sync,
                         int *ipiv, unsigned int epoch0, int *swap_dst,
                         int *swap_src, hipStream_t s);
 int conflux_panel_sync_bytes();
+int conflux_panel_err_offset();  // byte offset of the give-up word (u32)
 void conflux_panel_spin_read(void *sync, unsigned long long *out,
                              hipStream_t s);
 int conflux_panel_nb();
