@@ -258,6 +258,20 @@ void nanscan(Ctx &c, const char *tag, int k, const double *p, int64_t nelem) {
 // LAPACKE_dgetrf semantics (reference LUP, conflux_opt.hpp:143-166):
 // ipiv_out[i] = absolute panel row swapped with row i at column i (0-based).
 // ---------------------------------------------------------------------------
+// CONFLUX_PANEL_GLUE: 1 (default) = the fused two-launch inter-leaf glue,
+// 0 = the four-launch chain (rowperm pair, 32-wide solve, K=32 GEMM) it
+// replaces — kept as the fallback for ragged leaves and as the reference the
+// tests compare against.  Process-global; conflux_lu_debug_set_panel_glue
+// overrides it.
+int g_panel_glue = -1;
+int panel_glue_mode() {
+    if (g_panel_glue < 0) {
+        const char *e = getenv("CONFLUX_PANEL_GLUE");
+        g_panel_glue = e ? (atoi(e) != 0) : 1;
+    }
+    return g_panel_glue;
+}
+
 int factor_panel(Ctx &c, RankState &r, int n, std::vector<int> &ipiv_out) {
     const int v = c.v;
     const int NB = conflux_panel_nb();
@@ -268,7 +282,7 @@ int factor_panel(Ctx &c, RankState &r, int n, std::vector<int> &ipiv_out) {
     // one NB-wide leaf: persistent factor kernel + full-width rowperm (the
     // factor kernel composed the realized sub-panel-relative permutation;
     // applied in two parallel passes over the non-sub-panel columns)
-    auto leaf = [&](int jb) -> int {
+    auto leaf = [&](int jb, bool perm = true) -> int {
         const int nb = std::min(NB, nsteps - jb);
         const int m = n - jb;  // rows of the sub-panel
         if (launch_panel_factor(r.panel + i64(jb) * v + jb, v, m, nb, r.sync,
@@ -278,7 +292,7 @@ int factor_panel(Ctx &c, RankState &r, int n, std::vector<int> &ipiv_out) {
             return CONFLUX_LU_EINTERNAL;
         }
         c.epoch += nb;
-        if (v > nb)
+        if (perm && v > nb)
             launch_rowperm_skip(r.panel, v, r.d_swap, r.d_swap + 64, jb,
                                 2 * nb, jb, nb, v - nb, r.rowtmp, c.stream);
         return 0;
@@ -332,11 +346,31 @@ int factor_panel(Ctx &c, RankState &r, int n, std::vector<int> &ipiv_out) {
         rec(0, v);
         if (rc2) return rc2;
     } else {
+        const int glue = panel_glue_mode();
         for (int jb = 0; jb < nsteps; jb += NB) {
             const int nb = std::min(NB, nsteps - jb);
             const int m = n - jb;
-            if (leaf(jb)) return CONFLUX_LU_EINTERNAL;
-            if (jb + nb < v && m > nb) {
+            // fused glue (CONFLUX_PANEL_GLUE, default 1): a full 32-column
+            // leaf with columns to its right and rows below it takes two
+            // purpose-built launches, bitwise equal to the four-launch
+            // chain below.  The last leaf of a panel (nothing to its right)
+            // uses the prep kernel for its permutation alone.  Ragged
+            // leaves and row-less updates stay on the chain.
+            const bool fused = glue && nb == 32 && jb + nb < v && m > nb;
+            const bool fused_perm =
+                glue && nb == 32 && jb + nb == v && v > nb;
+            if (leaf(jb, !(fused || fused_perm))) return CONFLUX_LU_EINTERNAL;
+            if (fused || fused_perm)
+                launch_panel_glue_prep(
+                    r.panel, v, r.d_swap, r.d_swap + 64, jb, v - nb,
+                    fused ? r.panel + i64(jb) * v + jb : nullptr, v,
+                    c.stream);
+            if (fused) {
+                launch_panel_glue_update(r.panel + i64(jb + nb) * v + jb, v,
+                                         r.panel + i64(jb) * v + jb + nb, v,
+                                         r.panel + i64(jb + nb) * v + jb + nb,
+                                         v, m - nb, v - jb - nb, c.stream);
+            } else if (jb + nb < v && m > nb) {
                 // U block: rows jb..jb+nb of cols jb+nb..v
                 launch_trsm_left_lower_unit32(r.panel + i64(jb) * v + jb, v,
                                               r.panel + i64(jb) * v + jb + nb,
@@ -3172,6 +3206,14 @@ int conflux_lu_debug_rowmove_bench(int Ml, int64_t cols, int rows, int iters,
     (void)hipEventDestroy(a); (void)hipEventDestroy(b);
     (void)hipStreamDestroy(s);
     return CONFLUX_LU_OK;
+}
+
+// select the panel's inter-leaf glue for this process (1 = fused, 0 = the
+// four-launch chain); returns the previous mode
+int conflux_lu_debug_set_panel_glue(int mode) {
+    const int prev = panel_glue_mode();
+    g_panel_glue = mode != 0;
+    return prev;
 }
 
 int conflux_lu_debug_getrf(int n, int v, double *panel, int *ipiv_out) {

@@ -31,6 +31,9 @@
 #define DEVFN __device__ __forceinline__
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+// two adjacent doubles at an address that is only 8-byte aligned
+typedef double f64x2u __attribute__((ext_vector_type(2), aligned(8)));
 
 namespace ck {
 
@@ -1068,6 +1071,200 @@ __global__ __launch_bounds__(512, 4) void k_dgemm_f64_w8(
     }
 }
 
+// ---------------------------------------------------------------------------
+// fused inter-leaf glue of factor_panel: two launches per 32-column leaf in
+// place of gather + scatter + k_trsm_left_lower_unit32 + a K=32 k_dgemm_f64_w8.
+// No inter-block communication in either kernel; both reproduce the old
+// chain BIT FOR BIT (tests/test_panel_glue_gpu.py compares the two paths).
+// ---------------------------------------------------------------------------
+// k_panel_glue_prep: thread = one column of [0, skip0) u [skip0 + 32,
+// tot_cols + 32), the columns launch_rowperm_skip covers at skipn = 32.  It
+// reads the column's 64 listed source rows (row_base + src_idx[i]) into
+// registers, then stores them to rows dst_idx[i] + row_base: every read of a
+// column precedes every write of it in ONE thread's program order, columns
+// are disjoint between threads, so the permutation needs no staging buffer
+// and no barrier (the one barrier below only publishes L).  Entries 0..31 of the map have dst = i (the sub-panel's new
+// rows 0..31, see k_panel_factor's tail), so for a column right of the
+// sub-panel x[0..31] IS the U block's column and the unit-lower solve with
+// L (32 x 32, the sub-panel's own top block, in the skipped columns and so
+// never written here) runs on the registers before the store.  Each element
+// receives k_trsm_left_lower_unit32's chain of operations (x[r] -= l[r][i] *
+// x[i], i ascending, each contracted to one fma); only the order in which
+// independent chains are interleaved differs (see the loop).  The map's
+// identity padding repeats entry 0 (dst 0, the source of entry 0): row 0 is
+// not changed by a unit-lower solve, so the repeated stores carry the value
+// entry 0 stores.  L == nullptr: permutation only.
+__global__ __launch_bounds__(64) void k_panel_glue_prep(
+    double *mat, int64_t ld, const int *__restrict__ dst_idx,
+    const int *__restrict__ src_idx, int row_base, int skip0, int tot_cols,
+    const double *__restrict__ L, int64_t ldl) {
+    __shared__ double sL[32][33];
+    const int tid = threadIdx.x;
+    const int cc0 = blockIdx.x * 64;
+    // block-uniform: some column of this block lies right of the sub-panel
+    const bool right = L && cc0 + 63 >= skip0;
+    // L and the column are loaded together: the kernel is a chain of memory
+    // round trips (map -> column -> store) and each costs several us under
+    // the concurrent trailing GEMM, so L must not add one of its own
+    double lreg[16];
+    if (right) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int e = tid + j * 64;
+            lreg[j] = L[(int64_t)(e >> 5) * ldl + (e & 31)];
+        }
+    }
+    const int cc = cc0 + tid;
+    const bool active = cc < tot_cols;
+    const int64_t c = (cc < skip0) ? cc : cc + 32;
+    // the map is read with wave-uniform indices, i.e. by scalar loads, 16
+    // entries a load.  (Measured alternative: one vector load per array plus
+    // readlane broadcasts — 34 vs 27 us per launch under the trailing GEMM.)
+    double x[64];
+    if (active) {
+#pragma unroll
+        for (int i = 0; i < 64; ++i)
+            x[i] = mat[(int64_t)(row_base + src_idx[i]) * ld + c];
+    }
+    if (right) {  // block-uniform, so the barrier is legal here
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int e = tid + j * 64;
+            sL[e >> 5][e & 31] = lreg[j];
+        }
+        __syncthreads();
+        if (active && cc >= skip0) {
+            // column-oriented order: x[i] is final once steps 0..i-1 ran,
+            // and row r still receives its terms with i ascending — the
+            // same chain of fmas per element as the row-oriented loop of
+            // k_trsm_left_lower_unit32, with 31 - i independent ones a step
+#pragma unroll
+            for (int i = 0; i < 31; ++i) {
+                const double xi = x[i];
+#pragma unroll
+                for (int r = i + 1; r < 32; ++r) x[r] -= sL[r][i] * xi;
+            }
+        }
+    }
+    if (active) {
+#pragma unroll
+        for (int i = 0; i < 64; ++i)
+            mat[(int64_t)(dst_idx[i] + row_base) * ld + c] = x[i];
+    }
+}
+
+// k_panel_glue_update: C (M x N) -= A (M x 32) * B (32 x N), K = 32 only.
+// One (64*WM) x (32*WN) tile per block, one 64 x 32 sub-tile per wave (the
+// w8 kernel's 4 x 2 fragments of v_mfma_f64_16x16x4_f64).  The whole K is
+// staged once (one barrier, no K loop) and the C tile is loaded into
+// registers BEFORE the staging writes and the MFMAs, so its HBM latency
+// overlaps them; then one subtraction and the store.  Bit-identity with
+// k_dgemm_f64_w8 at K = 32: accumulators start at zero, the eight k-blocks
+// of 4 run ascending with the same lane -> k map, then C = C - acc.
+// __launch_bounds__(.., 3): three 256-thread blocks a CU is what the 50 KB
+// of LDS admits, and under the concurrent trailing GEMM the kernel's share
+// of the memory system follows the bytes it keeps in flight.
+template <int WM, int WN>
+__global__ __launch_bounds__(64 * WM * WN, 3) void k_panel_glue_update(
+    const double *__restrict__ A, int64_t lda, const double *__restrict__ B,
+    int64_t ldb, double *__restrict__ C, int64_t ldc, int M, int N) {
+    constexpr int K = 32, BM = 64 * WM, BN = 32 * WN, TPB = 64 * WM * WN;
+    constexpr int NA = BM * K / 2 / TPB;   // staged element PAIRS per thread
+    constexpr int NBE = K * BN / 2 / TPB;
+    __shared__ double As[K][BM + 1];   // transposed, padded
+    __shared__ alignas(16) double Bs[K][BN + 2];
+    const int row0 = blockIdx.y * BM;
+    const int col0 = blockIdx.x * BN;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int wm0 = (wave / WN) * 64;             // wave's 64x32 sub-tile
+    const int wn0 = (wave % WN) * 32;
+    const int frow = lane & 15;                   // fragment row/col lane part
+    const int fk = lane >> 4;                     // fragment k lane part
+    // Column assignment inside the wave's 32 columns: lane part frow of
+    // fragment j holds column 2*frow + j (not j*16 + frow), so a lane's two
+    // fragments are ADJACENT columns — every C access is 16 bytes a lane,
+    // half the requests of the 8-byte form, and one 16-byte LDS read feeds
+    // both B operands.  Which MFMA column slot an element sits in does not
+    // enter its arithmetic.
+    const int wc = wn0 + 2 * frow;                // tile column of fragment 0
+
+    // stage A (BM x 32) and B (32 x BN): two adjacent elements per access
+    f64x2u ra[NA], rb[NBE];
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+        const int e = tid + i * TPB;              // pair index, 16 per row
+        const int gr = row0 + (e >> 4);
+        ra[i] = (gr < M)
+                    ? *(const f64x2u *)&A[(int64_t)gr * lda + 2 * (e & 15)]
+                    : f64x2u{0, 0};
+    }
+#pragma unroll
+    for (int i = 0; i < NBE; ++i) {
+        const int e = tid + i * TPB;              // pair index, BN/2 per row
+        const int gc = col0 + 2 * (e % (BN / 2));
+        const double *bp = &B[(int64_t)(e / (BN / 2)) * ldb + gc];
+        rb[i] = (gc + 1 < N) ? *(const f64x2u *)bp
+                             : f64x2u{gc < N ? *bp : 0.0, 0.0};
+    }
+    // C prefetch (f64 16x16x4 C/D map: lane l, reg q -> D[4*q + (l>>4)][.]):
+    // issued before the staging writes and the MFMAs so its latency overlaps
+    // them.  cr[i][q] = the lane's two columns of row i*16 + q*4 + fk.
+    f64x2u cr[4][4];
+    const int gc0 = col0 + wc;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int r = row0 + wm0 + i * 16 + q * 4 + fk;
+            const double *cp = &C[(int64_t)r * ldc + gc0];
+            cr[i][q] = (r < M && gc0 + 1 < N)
+                           ? *(const f64x2u *)cp
+                           : f64x2u{(r < M && gc0 < N) ? *cp : 0.0, 0.0};
+        }
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+        const int e = tid + i * TPB;
+        As[2 * (e & 15)][e >> 4] = ra[i][0];
+        As[2 * (e & 15) + 1][e >> 4] = ra[i][1];
+    }
+#pragma unroll
+    for (int i = 0; i < NBE; ++i) {
+        const int e = tid + i * TPB;
+        *(f64x2 *)&Bs[e / (BN / 2)][2 * (e % (BN / 2))] =
+            f64x2{rb[i][0], rb[i][1]};
+    }
+    __syncthreads();
+
+    // one 16-row fragment pair at a time: 16 accumulator registers live
+    // instead of 64, which is what lets three blocks share a CU
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        f64x4 acc0 = f64x4{0, 0, 0, 0}, acc1 = f64x4{0, 0, 0, 0};
+#pragma unroll
+        for (int kk = 0; kk < K / 4; ++kk) {
+            const int k = kk * 4 + fk;
+            const double af = As[k][wm0 + i * 16 + frow];
+            const f64x2 bf = *(const f64x2 *)&Bs[k][wc];
+            acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(af, bf[0], acc0, 0, 0,
+                                                        0);
+            acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(af, bf[1], acc1, 0, 0,
+                                                        0);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int r = row0 + wm0 + i * 16 + q * 4 + fk;
+            double *cp = &C[(int64_t)r * ldc + gc0];
+            const f64x2u o = {cr[i][q][0] - acc0[q], cr[i][q][1] - acc1[q]};
+            if (r < M && gc0 + 1 < N)
+                *(f64x2u *)cp = o;
+            else if (r < M && gc0 < N)
+                *cp = o[0];
+        }
+    }
+}
+
 
 // 256x128 block-tile variant (CONFLUX_GEMM_VARIANT=3): 8 waves as 4x2 of
 // 64x64 fragments — double the accumulator chains per wave and half the
@@ -1665,6 +1862,45 @@ void launch_rowperm_skip(double *mat, int64_t ld, const int *dst_idx,
     hipLaunchKernelGGL(k_rowperm_scatter_skip, dim3(cap_grid(n)), dim3(256),
                        0, s, tmp, mat, ld, dst_idx, row_base, n_rows, skip0,
                        skipn, tot_cols);
+}
+
+// fused glue, step 1: the leaf's row permutation over the non-sub-panel
+// columns of a `tot_cols + 32`-wide panel (swap map of 64 entries, sub-panel
+// at columns [jb, jb + 32), rows relative to jb) and, with L != nullptr, the
+// unit-lower solve of rows jb..jb+31 of the columns right of the sub-panel
+void launch_panel_glue_prep(double *mat, int64_t ld, const int *dst_idx,
+                            const int *src_idx, int jb, int tot_cols,
+                            const double *L, int64_t ldl, hipStream_t s) {
+    if (tot_cols <= 0) return;
+    hipLaunchKernelGGL(k_panel_glue_prep, dim3((unsigned)cdiv64(tot_cols, 64)),
+                       dim3(64), 0, s, mat, ld, dst_idx, src_idx, jb, jb,
+                       tot_cols, L, ldl);
+}
+
+// fused glue, step 2: C (M x N) -= A (M x 32) B (32 x N).  Tile shape:
+// CONFLUX_GLUE_TILE = 0: 128x128, 1: 64x128, 2 (default): 128x64 — in
+// context the two 256-thread shapes tie and the 128x128 one gains nothing
+// over the old chain (sweep in DESIGN §9); 128x64 wastes the least of a tile
+// on the narrow last leaves.  Plain 2-D grid, one tile per block.
+void launch_panel_glue_update(const double *A, int64_t lda, const double *B,
+                              int64_t ldb, double *C, int64_t ldc, int M,
+                              int N, hipStream_t s) {
+    if (M <= 0 || N <= 0) return;
+    static int tile = -1;
+    if (tile < 0) {
+        const char *e = getenv("CONFLUX_GLUE_TILE");
+        tile = e ? atoi(e) : 2;
+        if (tile < 0 || tile > 2) tile = 2;
+    }
+#define GLUE_UPDATE(WM, WN)                                                   \
+    hipLaunchKernelGGL((k_panel_glue_update<WM, WN>),                         \
+                       dim3((unsigned)cdiv64(N, 32 * WN),                     \
+                            (unsigned)cdiv64(M, 64 * WM)),                    \
+                       dim3(64 * WM * WN), 0, s, A, lda, B, ldb, C, ldc, M, N)
+    if (tile == 0) GLUE_UPDATE(2, 4);
+    else if (tile == 1) GLUE_UPDATE(1, 4);
+    else GLUE_UPDATE(2, 2);
+#undef GLUE_UPDATE
 }
 
 // panel block shape: CONFLUX_PANEL_RPB (rows/block) x CONFLUX_PANEL_TPB

@@ -25,6 +25,18 @@ void launch_rowperm_skip(double *mat, int64_t ld, const int *dst_idx,
                          const int *src_idx, int row_base, int n_rows,
                          int64_t skip0, int64_t skipn, int64_t tot_cols,
                          double *tmp, hipStream_t s);
+// fused inter-leaf glue of factor_panel (32-column leaves only): prep = the
+// leaf's row permutation (sub-panel at columns [jb, jb+32) skipped, tot_cols
+// other columns, 64-entry swap map relative to row jb) plus, with L given,
+// the unit-lower solve of rows jb..jb+31 right of the sub-panel; update =
+// C (M x N) -= A (M x 32) B (32 x N).  Bitwise equal to launch_rowperm_skip
+// + launch_trsm_left_lower_unit32 + launch_dgemm_f64 at K = 32.
+void launch_panel_glue_prep(double *mat, int64_t ld, const int *dst_idx,
+                            const int *src_idx, int jb, int tot_cols,
+                            const double *L, int64_t ldl, hipStream_t s);
+void launch_panel_glue_update(const double *A, int64_t lda, const double *B,
+                              int64_t ldb, double *C, int64_t ldc, int M,
+                              int N, hipStream_t s);
 int launch_panel_factor(double *panel, int64_t ldp, int m, int nb, void *sync,
                         int *ipiv, unsigned int epoch0, int *swap_dst,
                         int *swap_src, hipStream_t s);
