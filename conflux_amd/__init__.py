@@ -60,6 +60,12 @@ def _load():
     lib.conflux_lu_debug_getrf.argtypes = [ctypes.c_int, ctypes.c_int,
                                            ctypes.c_void_p, ctypes.c_void_p]
     lib.conflux_lu_debug_set_panel_glue.argtypes = [ctypes.c_int]
+    lib.conflux_lu_debug_set_trsm_stripe.argtypes = [ctypes.c_int]
+    lib.conflux_lu_debug_trsm_stripe_width.argtypes = []
+    lib.conflux_lu_debug_trsm_ld.argtypes = [
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong,
+        ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p,
+        ctypes.c_void_p]
     lib.conflux_lu_debug_dgemm_bench.argtypes = [
         ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
         ctypes.POINTER(ctypes.c_double)]

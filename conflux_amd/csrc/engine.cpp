@@ -27,7 +27,6 @@
 #include <functional>
 #include <numeric>
 #include <string>
-#include <unordered_map>
 #include <set>
 #include <vector>
 
@@ -80,6 +79,7 @@ struct RankState {
     double *slabs = nullptr;    // Ml x v — A10 slab pack
     double *Fres = nullptr;     // Ml x Nl (store_factors only)
     double *A10hist = nullptr;  // Ml x Nl (store_factors only)
+    double *triws = nullptr;    // stripe-resident panel solves' scratch
     int *d_ipiv = nullptr;      // v
     int *d_swap = nullptr;      // 128: laswp dst/src row maps
     int *d_idx = nullptr;       // 4v: pivot rows / early / late / order
@@ -88,8 +88,10 @@ struct RankState {
     int *d_perm = nullptr;      // max(2v, Ml)
     void *sync = nullptr;       // PanelSync
     // host bookkeeping (identical across pj, pk for fixed pi, tracked per rank)
-    std::vector<int> gri;
-    std::unordered_map<int, int> igri;
+    std::vector<int> gri;       // Ml: global row at each local position
+    std::vector<int> igri;      // M: local position of a global row this
+                                // rank row owns, -1 elsewhere
+    int *h_idx = nullptr;       // pinned, 2 slots x 4v: staging for d_idx
     int fnp = 0, nact = 0;
 };
 
@@ -175,6 +177,8 @@ int alloc_rank(Ctx &c, RankState &r, int pi, int pj, int pk) {
     HIPCHK(hipMalloc(&r.d_perm, prows * 4));
     HIPCHK(hipMalloc(&r.sync, conflux_panel_sync_bytes()));
     HIPCHK(hipMemset(r.sync, 0, conflux_panel_sync_bytes()));
+    HIPCHK(hipHostMalloc(&r.h_idx, size_t(2) * 4 * v * 4));
+    std::memset(r.h_idx, 0, size_t(2) * 4 * v * 4);
     r.gri.resize(c.Ml);
     return 0;
 }
@@ -190,11 +194,12 @@ void free_rank(RankState &r) {
     for (double *p : {r.A11, r.A11in, r.A10, r.A01, r.A10Rcv, r.A01Rcv,
                       r.A10Rcv2, r.A01Rcv2,
                       r.A00, r.cand, r.panel, r.cm, r.A01pack, r.rowtmp,
-                      r.redtmp, r.slabs, r.Fres, r.A10hist})
+                      r.redtmp, r.slabs, r.Fres, r.A10hist, r.triws})
         if (p) (void)hipFree(p);
     for (int *p : {r.d_ipiv, r.d_swap, r.d_idx, r.d_gri, r.d_gpivots, r.d_perm})
         if (p) (void)hipFree(p);
     if (r.sync) (void)hipFree(r.sync);
+    if (r.h_idx) (void)hipHostFree(r.h_idx);
 }
 
 // timing bracket helpers ----------------------------------------------------
@@ -424,13 +429,61 @@ void ipiv_to_perm(const std::vector<int> &ipiv, int n, int v,
     for (int i = 0; i < std::min(v, n); ++i) std::swap(perm[i], perm[ipiv[i]]);
 }
 
+// CONFLUX_TRSM_STRIPE: 1 (default) = the stripe-resident fused solves (a
+// block keeps its stripe of X in LDS for the whole triangle), 0 = the
+// panel-streaming fused solves they replace — kept as the A/B baseline and
+// as the bitwise reference the tests compare against.  Where the stripe does
+// not fit the LDS for this v the streaming kernels run in either mode.
+// Process-global; conflux_lu_debug_set_trsm_stripe overrides it.
+int g_trsm_stripe = -1;
+int trsm_stripe_mode() {
+    if (g_trsm_stripe < 0) {
+        const char *e = getenv("CONFLUX_TRSM_STRIPE");
+        g_trsm_stripe = e ? (atoi(e) != 0) : 1;
+    }
+    return g_trsm_stripe;
+}
+
+// the stripe solves' scratch (block-major copy of the triangle): slot 0 for
+// the right solve, slot 1 for the left solve, which may run concurrently
+int stripe_ws(RankState &r, int v, int which, double **ws) {
+    const int64_t n = conflux_trsm_stripe_ws_doubles(v);
+    if (!r.triws) HIPCHK(hipMalloc(&r.triws, 2 * n * 8));
+    *ws = r.triws + which * n;
+    return 0;
+}
+
+// the fused single-launch solves on r.A00 (v % 32 == 0), by mode
+int fused_trsm_right(RankState &r, double *X, int64_t ldx, int v, int64_t M,
+                     int trans, hipStream_t s) {
+    if (trsm_stripe_mode() && conflux_trsm_stripe_fits(v)) {
+        double *ws;
+        if (stripe_ws(r, v, 0, &ws)) return CONFLUX_LU_EHIP;
+        launch_trsm_right_stripe(r.A00, v, X, ldx, v, M, trans, ws, s);
+    } else
+        launch_trsm_right_mfma(r.A00, v, X, ldx, v, M, trans, s);
+    return 0;
+}
+
+int fused_trsm_left(RankState &r, double *X, int64_t ldx, int v, int64_t N,
+                    hipStream_t s) {
+    if (trsm_stripe_mode() && conflux_trsm_stripe_fits(v)) {
+        double *ws;
+        if (stripe_ws(r, v, 1, &ws)) return CONFLUX_LU_EHIP;
+        launch_trsm_left_stripe(r.A00, v, X, ldx, v, N, ws, s);
+    } else
+        launch_trsm_left_mfma(r.A00, v, X, ldx, v, N, s);
+    return 0;
+}
+
 // blocked TRSMs on full panels (diag blocks of PANEL_NB + MFMA updates) -----
 int trsm_right_upper(Ctx &c, RankState &r, double *X, int64_t ldx, int M) {
     const int v = c.v, NB = conflux_panel_nb();
     size_t slot;
     if (ev_begin(c, 2, 0, &slot)) return CONFLUX_LU_EHIP;
     if (v % 32 == 0) {  // fused single-launch MFMA solve
-        launch_trsm_right_mfma(r.A00, v, X, ldx, v, M, 0, c.stream);
+        if (fused_trsm_right(r, X, ldx, v, M, 0, c.stream))
+            return CONFLUX_LU_EHIP;
         return ev_end(c, slot);
     }
     for (int jb = 0; jb < v; jb += NB) {
@@ -449,7 +502,7 @@ int trsm_left_lower(Ctx &c, RankState &r, double *X, int64_t ldx, int64_t N) {
     size_t slot;
     if (ev_begin(c, 2, 0, &slot)) return CONFLUX_LU_EHIP;
     if (v % 32 == 0) {  // fused single-launch MFMA solve
-        launch_trsm_left_mfma(r.A00, v, X, ldx, v, N, c.stream);
+        if (fused_trsm_left(r, X, ldx, v, N, c.stream)) return CONFLUX_LU_EHIP;
         return ev_end(c, slot);
     }
     for (int jb = 0; jb < v; jb += NB) {
@@ -719,6 +772,28 @@ void plan_from_gpivots(Ctx &c, StepPlan &sp) {
 int phase01(Ctx &c, int k, StepPlan &sp);
 int run_step(Ctx &c, int k, StepPlan &sp);
 
+// CONFLUX_GAP_STATS=1: host wall time of the serial stretch between two panel
+// chains, accumulated over run_step calls and printed to stderr after each
+// factorization: run_step entry -> first TRSM enqueue, the gri/igri update
+// alone, run_step entry -> the ev_pc record.  Off by default (no clock reads).
+struct GapStats {
+    double to_trsm = 0, gri = 0, to_evpc = 0;
+    long steps = 0, evpc_steps = 0;
+};
+GapStats g_gap;
+bool gap_stats_on() {
+    static int on = -1;
+    if (on < 0) {
+        const char *e = getenv("CONFLUX_GAP_STATS");
+        on = e ? atoi(e) != 0 : 0;
+    }
+    return on != 0;
+}
+using GapClock = std::chrono::steady_clock;
+inline double gap_ms(GapClock::time_point a, GapClock::time_point b) {
+    return std::chrono::duration<double, std::milli>(b - a).count();
+}
+
 int factor_loop(Ctx &c, double *elapsed_ms) {
     // reset per-factor state
     for (auto &r : c.rs) {
@@ -726,7 +801,7 @@ int factor_loop(Ctx &c, double *elapsed_ms) {
         r.nact = c.Ml;
         for (int i = 0; i < c.Ml; ++i)
             r.gri[i] = (i / c.v * c.Px + r.pi) * c.v + i % c.v;
-        r.igri.clear();
+        r.igri.assign(c.M, -1);
         for (int i = 0; i < c.Ml; ++i) r.igri[r.gri[i]] = i;
         HIPCHK(hipMemcpyAsync(r.d_gri, r.gri.data(), c.Ml * 4,
                               hipMemcpyHostToDevice, c.stream));
@@ -739,6 +814,7 @@ int factor_loop(Ctx &c, double *elapsed_ms) {
     c.pivotInds.assign(c.M, -1);
     c.evs_used = 0;
     for (auto &t : c.cats) t = TimeCat{};
+    g_gap = GapStats{};
 
     int rc = timed_region(c, elapsed_ms, [&]() -> int {
         StepPlan sp;
@@ -764,6 +840,12 @@ int factor_loop(Ctx &c, double *elapsed_ms) {
                          r.grank, sp2);
         }
     }
+    if (gap_stats_on())
+        std::fprintf(stderr,
+                     "[gapstats] steps=%ld entry->trsm=%.3f ms  gri/igri=%.3f "
+                     "ms  entry->ev_pc=%.3f ms (%ld steps)\n",
+                     g_gap.steps, g_gap.to_trsm, g_gap.gri, g_gap.to_evpc,
+                     g_gap.evpc_steps);
     return 0;
 }
 
@@ -982,6 +1064,9 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
     const bool look = (k + 1 < c.Nt);
     const int ncol = (k + 1) % Py;
     const int64_t lnext = i64(v) * ((k + 1) / Py);
+    const bool gap_on = gap_stats_on();
+    GapClock::time_point gap_t0;
+    if (gap_on) gap_t0 = GapClock::now();
 
     // ---- step 2: push pivot rows up, pack, depth-reduce (C7) --------------
     for (auto &r : c.rs) {
@@ -989,47 +1074,58 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
         const auto &ord = sp.order[r.pi];
         const int cnt = (int)lr.size();
         const int f = r.fnp;
-        std::vector<int> lrows_loc(cnt);
-        for (int i = 0; i < cnt; ++i) lrows_loc[i] = r.igri.at(lr[i]);
-        std::vector<char> is_piv(c.Ml, 0);
-        for (int i : lrows_loc) is_piv[i] = 1;
-        std::vector<int> early, late;
-        for (int i = f; i < std::min(f + cnt, c.Ml); ++i)
-            if (!is_piv[i]) early.push_back(i);
-        for (int i = f + cnt; i < c.Ml; ++i)
-            if (is_piv[i]) late.push_back(i);
-        if (early.size() != late.size()) {
+        // this step's index lists are built in one pinned staging slot and
+        // go up in one copy; layout (= d_idx): [0,v) lrows, [v,2v) early,
+        // [2v,3v) late, [3v,4v) order.  Two slots alternate by step, so a
+        // slot is rewritten only after a later step's panel download has
+        // synchronized past the copy that read it.
+        int *const stage = r.h_idx + (k & 1) * 4 * v;
+        int *const lrows_loc = stage, *const early = stage + v,
+                   *const late = stage + 2 * v;
+        // host work proportional to the rows that move, not to Ml: only
+        // positions [f, f+cnt) and the pivot rows' own positions matter
+        const int wend = std::min(f + cnt, c.Ml);
+        std::vector<char> in_win(std::max(wend - f, 0), 0);
+        int n_early = 0, n_late = 0;
+        for (int i = 0; i < cnt; ++i) {
+            const int p = (lr[i] >= 0 && lr[i] < c.M) ? r.igri[lr[i]] : -1;
+            if (p < 0) {
+                c.err = "pivot push: global row " + std::to_string(lr[i]) +
+                        " is not on rank row " + std::to_string(r.pi) +
+                        " (k=" + std::to_string(k) + ")";
+                return CONFLUX_LU_EINTERNAL;
+            }
+            lrows_loc[i] = p;
+            stage[3 * v + i] = ord[i];
+            if (p >= f && p < wend)
+                in_win[p - f] = 1;
+            else if (p >= f + cnt)
+                late[n_late++] = p;
+        }
+        std::sort(late, late + n_late);
+        n_late = (int)(std::unique(late, late + n_late) - late);
+        for (int i = f; i < wend; ++i)
+            if (!in_win[i - f]) early[n_early++] = i;
+        if (n_early != n_late) {
             std::set<int> uniq(lr.begin(), lr.end());
             c.err = "pivot push invariant: k=" + std::to_string(k) +
                     " cnt=" + std::to_string(cnt) +
                     " uniq=" + std::to_string(uniq.size()) +
-                    " early=" + std::to_string(early.size()) +
-                    " late=" + std::to_string(late.size()) +
+                    " early=" + std::to_string(n_early) +
+                    " late=" + std::to_string(n_late) +
                     " f=" + std::to_string(f);
             return CONFLUX_LU_EINTERNAL;
         }
-        // idx layout in d_idx: [0,v) lrows, [v,2v) early, [2v,3v) late,
-        // [3v,4v) order
-        if (cnt) {
-            HIPCHK(hipMemcpyAsync(r.d_idx, lrows_loc.data(), cnt * 4,
+        if (cnt)
+            HIPCHK(hipMemcpyAsync(r.d_idx, stage, size_t(4) * v * 4,
                                   hipMemcpyHostToDevice, c.stream));
-            HIPCHK(hipMemcpyAsync(r.d_idx + 3 * v, ord.data(), cnt * 4,
-                                  hipMemcpyHostToDevice, c.stream));
-        }
-        if (!early.empty()) {
-            HIPCHK(hipMemcpyAsync(r.d_idx + v, early.data(), early.size() * 4,
-                                  hipMemcpyHostToDevice, c.stream));
-            HIPCHK(hipMemcpyAsync(r.d_idx + 2 * v, late.data(),
-                                  late.size() * 4, hipMemcpyHostToDevice,
-                                  c.stream));
-        }
         auto push = [&](double *mat, int64_t ld, int64_t cols) -> int {
             size_t slot;
             if (ev_begin(c, 3, 0, &slot)) return CONFLUX_LU_EHIP;
             launch_row_gather(mat, ld, r.rowtmp, cols, r.d_idx, cnt, cols,
                               c.stream);
             launch_row_move(mat, ld, mat, ld, r.d_idx + v, r.d_idx + 2 * v,
-                            (int)early.size(), cols, c.stream);
+                            n_early, cols, c.stream);
             launch_copy2d(r.rowtmp, cols, mat + i64(f) * ld, ld, cnt, cols,
                           c.stream);
             return ev_end(c, slot);
@@ -1039,15 +1135,28 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
         if (c.store_factors && push(r.A10hist, Nl, Nl)) return CONFLUX_LU_EHIP;
         // host gri/igri update (identical shuffle)
         {
+            GapClock::time_point gri_t0;
+            if (gap_on) gri_t0 = GapClock::now();
             std::vector<int> tmp(cnt);
             for (int i = 0; i < cnt; ++i) tmp[i] = r.gri[lrows_loc[i]];
-            for (size_t i = 0; i < late.size(); ++i)
+            for (int i = 0; i < n_late; ++i) {
                 r.gri[late[i]] = r.gri[early[i]];
-            for (int i = 0; i < cnt; ++i) r.gri[f + i] = tmp[i];
-            r.igri.clear();
-            for (int i = 0; i < c.Ml; ++i) r.igri[r.gri[i]] = i;
-            HIPCHK(hipMemcpyAsync(r.d_gri, r.gri.data(), c.Ml * 4,
-                                  hipMemcpyHostToDevice, c.stream));
+                r.igri[r.gri[late[i]]] = late[i];
+            }
+            for (int i = 0; i < cnt; ++i) {
+                r.gri[f + i] = tmp[i];
+                r.igri[tmp[i]] = f + i;
+            }
+            // d_gri's only device reader is the tournament's candidate pack
+            // (phase01, grids with Px > 1); positions outside [f, last late
+            // row] did not change
+            if (Px > 1 && cnt) {
+                const int hi = n_late ? late[n_late - 1] + 1 : f + cnt;
+                HIPCHK(hipMemcpyAsync(r.d_gri + f, r.gri.data() + f,
+                                      size_t(hi - f) * 4,
+                                      hipMemcpyHostToDevice, c.stream));
+            }
+            if (gap_on) g_gap.gri += gap_ms(gri_t0, GapClock::now());
         }
         r.fnp += cnt;
         r.nact -= cnt;
@@ -1230,6 +1339,10 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
         if (r.pj == kcol)  // diagonal tile: packed LU from A00
             launch_copy2d(r.A00, v, Frow + loff, Nl, v, v, c.stream);
     };
+    if (gap_on) {
+        g_gap.to_trsm += gap_ms(gap_t0, GapClock::now());
+        ++g_gap.steps;
+    }
     if (split_trsm) {
         HIPCHK(hipEventRecord(c.ev_t3, c.stream));
         HIPCHK(hipStreamWaitEvent(c.trsm_stream, c.ev_t3, 0));
@@ -1380,6 +1493,10 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
                         r.A11 + i64(r.fnp) * Nl + lnext, i64(r.nact) * Nl);
     if (look && !c.sim && c.panel_stream) {
         HIPCHK(hipEventRecord(c.ev_pc, c.stream));
+        if (gap_on) {
+            g_gap.to_evpc += gap_ms(gap_t0, GapClock::now());
+            ++g_gap.evpc_steps;
+        }
     }
     if (slice_first) {
         // rest of the A01 solve feeds the (b) pieces below
@@ -1479,7 +1596,8 @@ int trsm_right_lowT(Ctx &c, RankState &r, double *X, int64_t ldx, int M) {
     size_t slot;
     if (ev_begin(c, 2, 0, &slot)) return CONFLUX_LU_EHIP;
     if (v % 32 == 0) {  // fused single-launch MFMA solve (X * L^-T)
-        launch_trsm_right_mfma(r.A00, v, X, ldx, v, M, 1, c.stream);
+        if (fused_trsm_right(r, X, ldx, v, M, 1, c.stream))
+            return CONFLUX_LU_EHIP;
         return ev_end(c, slot);
     }
     for (int jb = 0; jb < v; jb += NB) {
@@ -3261,9 +3379,55 @@ int conflux_lu_debug_trsm(int side_right, int M_or_v, int64_t N_or_M,
     HIPCHK(hipStreamSynchronize(c.stream));
     if (!rc) HIPCHK(hipMemcpy(X, dX, xsz * 8, hipMemcpyDeviceToHost));
     (void)hipFree(r.A00); (void)hipFree(dX);
+    if (r.triws) (void)hipFree(r.triws);
     for (auto &e : c.evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     (void)hipStreamDestroy(c.stream);
     (void)M_or_v;
+    return rc;
+}
+
+// select the fused panel solves for this process (1 = stripe-resident, 0 =
+// panel-streaming); returns the previous mode
+int conflux_lu_debug_set_trsm_stripe(int mode) {
+    const int prev = trsm_stripe_mode();
+    g_trsm_stripe = mode != 0;
+    return prev;
+}
+
+// columns (left solve) / rows (right solve) one block of the stripe-resident
+// solves owns
+int conflux_lu_debug_trsm_stripe_width() { return conflux_trsm_stripe_width(); }
+
+// conflux_lu_debug_trsm on a window of a wider host array X with leading
+// dimension ldx: side_right -> X[0:n, off:off+v] <- that * U^-1 (trans=0, T
+// upper) or * L^-T (trans=1, T lower; the Cholesky solve); else
+// X[0:v, off:off+n] <- L^-1 * that (T unit lower).  Nothing outside the
+// window is written.
+int conflux_lu_debug_trsm_ld(int side_right, int trans, int v, int64_t n,
+                             int64_t ldx, int64_t off, const double *T,
+                             double *X) {
+    if (v <= 0 || n <= 0 || off < 0 || !T || !X ||
+        ldx < off + (side_right ? i64(v) : n) || n > INT32_MAX)
+        return CONFLUX_LU_EARG;
+    Ctx c;
+    c.v = v;
+    HIPCHK(hipStreamCreate(&c.stream));
+    RankState r;
+    HIPCHK(hipMalloc(&r.A00, i64(v) * v * 8));
+    HIPCHK(hipMemcpy(r.A00, T, i64(v) * v * 8, hipMemcpyHostToDevice));
+    double *dX;
+    const int64_t xsz = (side_right ? n : i64(v)) * ldx;
+    HIPCHK(hipMalloc(&dX, xsz * 8));
+    HIPCHK(hipMemcpy(dX, X, xsz * 8, hipMemcpyHostToDevice));
+    int rc = !side_right ? trsm_left_lower(c, r, dX + off, ldx, n)
+             : trans     ? trsm_right_lowT(c, r, dX + off, ldx, (int)n)
+                         : trsm_right_upper(c, r, dX + off, ldx, (int)n);
+    HIPCHK(hipStreamSynchronize(c.stream));
+    if (!rc) HIPCHK(hipMemcpy(X, dX, xsz * 8, hipMemcpyDeviceToHost));
+    (void)hipFree(r.A00); (void)hipFree(dX);
+    if (r.triws) (void)hipFree(r.triws);
+    for (auto &e : c.evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
+    (void)hipStreamDestroy(c.stream);
     return rc;
 }
 

@@ -2256,6 +2256,248 @@ __global__ __launch_bounds__(256) void k_trsm_left_mfma(
     }
 }
 
+// ---------------------------------------------------------------------------
+// Stripe-resident editions of the two fused solves.  The kernels above
+// re-read every solved 32-wide panel of their stripe from global memory for
+// each diagonal block (v/32 * (v/32 - 1) / 2 staged panels per launch, each
+// a load -> LDS write -> barrier hop), which makes them latency chains whose
+// time does not depend on the width of X.  Here a block loads a TRS_W-wide
+// stripe ONCE, keeps all v/32 panels in LDS for its life and writes the
+// stripe back once; inside the jb/pb loops only the 32x32 triangle blocks
+// come from global memory (L2-resident, from a block-major copy made by
+// k_trsm_pack_tri), prefetched into registers one item ahead of the barrier
+// chain.  Every element sees the operations of the
+// kernels above in the same order (left-looking over pb, a fresh accumulator
+// per pb, the same eight MFMAs with k = 4*kk + fk, X -= acc, the same
+// diagonal solve), so the results are bit-identical; rows (right) and
+// columns (left) of X are independent, so the narrower stripe changes no sum.
+// One wave per 16x16 output tile: 4 waves, one per SIMD, one block per CU.
+// ---------------------------------------------------------------------------
+#define TRS_W 32
+#define TRS_MAXP 16  // panels resident: v <= 512 -> 18 * 8448 B = 148.5 KiB
+
+// Every block of a stripe solve reads the whole triangle, one 32x32 block
+// per item, all blocks at about the same time.  In place (ld = v = 512
+// doubles) the 32 rows of a block lie 4 KiB apart, so the whole chip's reads
+// of an item queue up on the few L2 channels those rows share.  The triangle
+// is therefore first copied block-major (8 KiB contiguous per block, in the
+// order the solves consume them: block (pb, jb), pb <= jb, at index
+// jb/32 * (jb/32 + 1) / 2 + pb/32), already oriented as the solve stages it:
+//   P[r][c] = T[(pb + r) * ld + jb + c]   swap = 0, tr = 0  (X U^-1)
+//   P[r][c] = T[(jb + c) * ld + pb + r]   swap = 1, tr = 1  (X L^-T)
+//   P[r][c] = T[(jb + r) * ld + pb + c]   swap = 1, tr = 0  (L^-1 X)
+__global__ __launch_bounds__(256) void k_trsm_pack_tri(
+    const double *__restrict__ T, int64_t ld, double *__restrict__ P, int swap,
+    int tr) {
+    int j = 0;
+    while ((j + 1) * (j + 2) / 2 <= (int)blockIdx.x) ++j;
+    const int pb = ((int)blockIdx.x - j * (j + 1) / 2) * 32, jb = j * 32;
+    const int rb = swap ? jb : pb, cb = swap ? pb : jb;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int e = threadIdx.x + i * 256;
+        const int r = e >> 5, c = e & 31;
+        P[(int64_t)blockIdx.x * 1024 + e] =
+            T[(int64_t)(rb + (tr ? c : r)) * ld + cb + (tr ? r : c)];
+    }
+}
+
+__device__ inline int trs_blk(int pb, int jb) {
+    return ((jb >> 5) * ((jb >> 5) + 1) / 2 + (pb >> 5)) * 1024;
+}
+
+// X (M x v, row-major) <- X * U^-1 or X * L^-T; U = the packed triangle.
+__global__ __launch_bounds__(256) void k_trsm_right_stripe(
+    const double *__restrict__ U, double *__restrict__ X, int64_t ldx, int v,
+    int64_t M) {
+    __shared__ double sX[TRS_MAXP][TRS_W][33];  // [panel][row][col]
+    __shared__ double sU[2][32][33];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int frow = lane & 15, fk = lane >> 4;
+    const int rt = wave >> 1, ct = wave & 1;  // this wave's 16x16 tile
+    const int64_t r0 = (int64_t)blockIdx.x * TRS_W;
+    const int rows = (int)min((int64_t)TRS_W, M - r0);
+    double ru[4];
+    auto load_u_regs = [&](int pb, int jb) {  // pb == jb: the diagonal block
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ru[i] = U[trs_blk(pb, jb) + tid + i * 256];
+    };
+    auto write_u = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = tid + i * 256;
+            sU[buf][e >> 5][e & 31] = ru[i];
+        }
+    };
+    load_u_regs(0, 0);
+    for (int i = tid; i < TRS_W * v; i += 256) {
+        const int r = i / v, cc = i - r * v;
+        sX[cc >> 5][r][cc & 31] = r < rows ? X[(r0 + r) * ldx + cc] : 0.0;
+    }
+    write_u(0);
+    __syncthreads();
+    int cur = 0;
+    for (int jb = 0; jb < v; jb += 32) {
+        double(*sXj)[33] = sX[jb >> 5];
+        for (int pb = 0; pb < jb; pb += 32) {
+            load_u_regs(pb + 32, jb);  // next update block, or the diagonal
+            const double(*sXp)[33] = sX[pb >> 5];
+            f64x4 acc = {0, 0, 0, 0};
+#pragma unroll
+            for (int kk = 0; kk < 8; ++kk) {
+                const int k = kk * 4 + fk;
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(
+                    sXp[rt * 16 + frow][k], sU[cur][k][ct * 16 + frow], acc, 0,
+                    0, 0);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                sXj[rt * 16 + 4 * q + fk][ct * 16 + frow] -= acc[q];
+            write_u(cur ^ 1);
+            __syncthreads();
+            cur ^= 1;
+        }
+        // sU[cur] holds the diagonal block; fetch the next jb's first update
+        // block behind the solve
+        const bool more = jb + 32 < v;
+        if (more) load_u_regs(0, jb + 32);
+        if (tid < rows) {  // diagonal solve: thread = row, register triangle
+            double x[32];
+#pragma unroll
+            for (int c = 0; c < 32; ++c) x[c] = sXj[tid][c];
+#pragma unroll
+            for (int c = 0; c < 32; ++c) {
+                double acc = x[c];
+#pragma unroll
+                for (int i = 0; i < 32; ++i)
+                    if (i < c) acc -= x[i] * sU[cur][i][c];
+                x[c] = acc / sU[cur][c][c];
+            }
+#pragma unroll
+            for (int c = 0; c < 32; ++c) sXj[tid][c] = x[c];
+        }
+        if (more) write_u(cur ^ 1);
+        __syncthreads();
+        cur ^= 1;
+    }
+    for (int i = tid; i < rows * v; i += 256) {
+        const int r = i / v, cc = i - r * v;
+        X[(r0 + r) * ldx + cc] = sX[cc >> 5][r][cc & 31];
+    }
+}
+
+// X (v x N, row-major) <- L^-1 * X, L unit lower = the packed triangle.
+__global__ __launch_bounds__(256) void k_trsm_left_stripe(
+    const double *__restrict__ L, double *__restrict__ X, int64_t ldx, int v,
+    int64_t N) {
+    __shared__ double sX[TRS_MAXP][32][TRS_W + 1];  // [panel][k][col]
+    __shared__ double sL[2][32][33];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int frow = lane & 15, fk = lane >> 4;
+    const int rt = wave >> 1, ct = wave & 1;  // this wave's 16x16 tile
+    const int64_t c0 = (int64_t)blockIdx.x * TRS_W;
+    const int cols = (int)min((int64_t)TRS_W, N - c0);
+    double rl[4];
+    auto load_l_regs = [&](int pb, int jb) {  // pb == jb: the diagonal block
+#pragma unroll
+        for (int i = 0; i < 4; ++i) rl[i] = L[trs_blk(pb, jb) + tid + i * 256];
+    };
+    auto write_l = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = tid + i * 256;
+            sL[buf][e >> 5][e & 31] = rl[i];
+        }
+    };
+    load_l_regs(0, 0);
+    for (int i = tid; i < v * TRS_W; i += 256) {
+        const int r = i >> 5, cc = i & (TRS_W - 1);
+        sX[r >> 5][r & 31][cc] =
+            cc < cols ? X[(int64_t)r * ldx + c0 + cc] : 0.0;
+    }
+    write_l(0);
+    __syncthreads();
+    int cur = 0;
+    for (int jb = 0; jb < v; jb += 32) {
+        double(*sXj)[TRS_W + 1] = sX[jb >> 5];
+        for (int pb = 0; pb < jb; pb += 32) {
+            load_l_regs(pb + 32, jb);  // next update block, or the diagonal
+            const double(*sXp)[TRS_W + 1] = sX[pb >> 5];
+            f64x4 acc = {0, 0, 0, 0};
+#pragma unroll
+            for (int kk = 0; kk < 8; ++kk) {
+                const int k = kk * 4 + fk;
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(
+                    sL[cur][rt * 16 + frow][k], sXp[k][ct * 16 + frow], acc, 0,
+                    0, 0);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                sXj[rt * 16 + 4 * q + fk][ct * 16 + frow] -= acc[q];
+            write_l(cur ^ 1);
+            __syncthreads();
+            cur ^= 1;
+        }
+        const bool more = jb + 32 < v;
+        if (more) load_l_regs(0, jb + 32);
+        if (tid < cols) {  // diagonal solve: thread = column, unit lower
+            double x[32];
+#pragma unroll
+            for (int r = 0; r < 32; ++r) x[r] = sXj[r][tid];
+#pragma unroll
+            for (int k = 0; k < 32; ++k) {
+                const double xk = x[k];
+#pragma unroll
+                for (int r = 0; r < 32; ++r)
+                    if (r > k) x[r] -= sL[cur][r][k] * xk;
+            }
+#pragma unroll
+            for (int r = 0; r < 32; ++r) sXj[r][tid] = x[r];
+        }
+        if (more) write_l(cur ^ 1);
+        __syncthreads();
+        cur ^= 1;
+    }
+    for (int i = tid; i < v * TRS_W; i += 256) {
+        const int r = i >> 5, cc = i & (TRS_W - 1);
+        if (cc < cols) X[(int64_t)r * ldx + c0 + cc] = sX[r >> 5][r & 31][cc];
+    }
+}
+
+int conflux_trsm_stripe_width() { return TRS_W; }
+bool conflux_trsm_stripe_fits(int v) {
+    return v > 0 && v % 32 == 0 && v <= 32 * TRS_MAXP;
+}
+
+int64_t conflux_trsm_stripe_ws_doubles(int v) {
+    const int64_t np = v / 32;
+    return np * (np + 1) / 2 * 1024;
+}
+
+void launch_trsm_right_stripe(const double *U, int64_t ldu, double *X,
+                              int64_t ldx, int v, int64_t M, int trans,
+                              double *ws, hipStream_t s) {
+    if (M <= 0 || v <= 0) return;
+    const int nblk = (int)(conflux_trsm_stripe_ws_doubles(v) / 1024);
+    hipLaunchKernelGGL(k_trsm_pack_tri, dim3(nblk), dim3(256), 0, s, U, ldu, ws,
+                       trans ? 1 : 0, trans ? 1 : 0);
+    hipLaunchKernelGGL(k_trsm_right_stripe, dim3(cdiv64(M, TRS_W)), dim3(256),
+                       0, s, ws, X, ldx, v, M);
+}
+
+void launch_trsm_left_stripe(const double *L, int64_t ldl, double *X,
+                             int64_t ldx, int v, int64_t N, double *ws,
+                             hipStream_t s) {
+    if (N <= 0 || v <= 0) return;
+    const int nblk = (int)(conflux_trsm_stripe_ws_doubles(v) / 1024);
+    hipLaunchKernelGGL(k_trsm_pack_tri, dim3(nblk), dim3(256), 0, s, L, ldl, ws,
+                       1, 0);
+    hipLaunchKernelGGL(k_trsm_left_stripe, dim3(cdiv64(N, TRS_W)), dim3(256),
+                       0, s, ws, X, ldx, v, N);
+}
+
 void launch_trsm_right_mfma(const double *U, int64_t ldu, double *X,
                             int64_t ldx, int v, int64_t M, int trans,
                             hipStream_t s) {

@@ -58,6 +58,20 @@ void launch_trsm_right_mfma(const double *U, int64_t ldu, double *X,
                             hipStream_t s);
 void launch_trsm_left_mfma(const double *L, int64_t ldl, double *X,
                            int64_t ldx, int v, int64_t N, hipStream_t s);
+// stripe-resident editions of the two fused solves (bit-identical to them):
+// a block keeps its 32-wide stripe of X in LDS for the whole triangle.
+// conflux_trsm_stripe_fits(v): v % 32 == 0 and the stripe fits the LDS.
+// ws: conflux_trsm_stripe_ws_doubles(v) doubles of device scratch per
+// launch in flight; the launch first copies the triangle into it block-major.
+int conflux_trsm_stripe_width();
+bool conflux_trsm_stripe_fits(int v);
+int64_t conflux_trsm_stripe_ws_doubles(int v);
+void launch_trsm_right_stripe(const double *U, int64_t ldu, double *X,
+                              int64_t ldx, int v, int64_t M, int trans,
+                              double *ws, hipStream_t s);
+void launch_trsm_left_stripe(const double *L, int64_t ldl, double *X,
+                             int64_t ldx, int v, int64_t N, double *ws,
+                             hipStream_t s);
 // solve_kernels.hip: X (v x N) <- T^-1 X, T lower/upper, unit/non-unit, any
 // v >= 1, read in place (ldt = the global N); C (M x nrhs) -= A B, nrhs <= 16
 void launch_trsm_left_tri_mfma(const double *T, int64_t ldt, double *X,
