@@ -60,6 +60,10 @@ def _load():
     lib.conflux_lu_debug_getrf.argtypes = [ctypes.c_int, ctypes.c_int,
                                            ctypes.c_void_p, ctypes.c_void_p]
     lib.conflux_lu_debug_set_panel_glue.argtypes = [ctypes.c_int]
+    lib.conflux_lu_debug_set_panel_reg.argtypes = [ctypes.c_int]
+    lib.conflux_lu_debug_set_panel_publish.argtypes = [ctypes.c_int]
+    lib.conflux_lu_debug_set_panel_phase_stats.argtypes = [ctypes.c_int]
+    lib.conflux_lu_debug_panel_phase_stats.argtypes = [ctypes.c_void_p]
     lib.conflux_lu_debug_set_trsm_stripe.argtypes = [ctypes.c_int]
     lib.conflux_lu_debug_trsm_stripe_width.argtypes = []
     lib.conflux_lu_debug_trsm_ld.argtypes = [

@@ -277,6 +277,13 @@ int panel_glue_mode() {
     return g_panel_glue;
 }
 
+// CONFLUX_PANEL_PHASE_STATS=1: host-side totals of the instrumented leaf
+// kernels' phase cycles (four phases over all blocks, then block 0's four)
+// and the number of columns they cover; factor_panel adds to them after
+// every panel, conflux_lu_debug_panel_phase_stats reads and resets them.
+unsigned long long g_panel_phase_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+unsigned long long g_panel_phase_cols = 0;
+
 int factor_panel(Ctx &c, RankState &r, int n, std::vector<int> &ipiv_out) {
     const int v = c.v;
     const int NB = conflux_panel_nb();
@@ -410,9 +417,21 @@ int factor_panel(Ctx &c, RankState &r, int n, std::vector<int> &ipiv_out) {
     HIPCHK(hipStreamSynchronize(c.stream));
     if (perr) {
         HIPCHK(hipMemsetAsync(d_err, 0, 4, c.stream));
-        c.err = "panel hand-off timed out: column code " +
-                std::to_string(perr) + " (1 + sub-panel column)";
+        if (perr >= 0x10000u)
+            c.err = "panel hand-off timed out in the granule payload "
+                    "re-read: column code " +
+                    std::to_string(perr - 0x10000u) +
+                    " (1 + sub-panel column)";
+        else
+            c.err = "panel hand-off timed out in the key poll: column code " +
+                    std::to_string(perr) + " (1 + sub-panel column)";
         return CONFLUX_LU_EINTERNAL;
+    }
+    if (conflux_panel_phase_stats_mode()) {
+        unsigned long long ph[8];
+        conflux_panel_phase_read(r.sync, ph, c.stream);
+        for (int i = 0; i < 8; ++i) g_panel_phase_acc[i] += ph[i];
+        g_panel_phase_cols += nsteps;
     }
     for (int jb = 0; jb < nsteps; jb += NB) {
         const int nb = std::min(NB, nsteps - jb);
@@ -839,6 +858,17 @@ int factor_loop(Ctx &c, double *elapsed_ms) {
             std::fprintf(stderr, "[spinstats] rank %d spins=%llu\n",
                          r.grank, sp2);
         }
+    }
+    if (conflux_panel_phase_stats_mode() && g_panel_phase_cols) {
+        const unsigned long long *p = g_panel_phase_acc;
+        std::fprintf(stderr,
+                     "[phasestats] cols=%llu cycles all blocks: wait=%llu "
+                     "load=%llu update=%llu publish=%llu | block 0: wait=%llu "
+                     "load=%llu update=%llu publish=%llu\n",
+                     g_panel_phase_cols, p[0], p[1], p[2], p[3], p[4], p[5],
+                     p[6], p[7]);
+        for (auto &x : g_panel_phase_acc) x = 0;
+        g_panel_phase_cols = 0;
     }
     if (gap_stats_on())
         std::fprintf(stderr,
@@ -3332,6 +3362,39 @@ int conflux_lu_debug_set_panel_glue(int mode) {
     const int prev = panel_glue_mode();
     g_panel_glue = mode != 0;
     return prev;
+}
+
+// select the leaf kernel of full 32-column leaves for this process (1 = the
+// register-resident k_panel_factor_reg, 0 = k_panel_factor); returns the
+// previous mode
+int conflux_lu_debug_set_panel_reg(int mode) {
+    return conflux_panel_set_reg_mode(mode);
+}
+
+// select the register leaf's hand-off form (1 = drain-free granule payload,
+// 0 = sc1 payload, drain, key); returns the previous mode
+int conflux_lu_debug_set_panel_publish(int mode) {
+    return conflux_panel_set_publish_mode(mode);
+}
+
+// switch the instrumented leaf kernels on or off (CONFLUX_PANEL_PHASE_STATS);
+// returns the previous mode
+int conflux_lu_debug_set_panel_phase_stats(int mode) {
+    return conflux_panel_set_phase_stats_mode(mode);
+}
+
+// the phase totals gathered since the last call: out9[0..3] cycles of wave 0
+// summed over all blocks (poll wait, load, update, publish), out9[4..7] block
+// 0's, out9[8] the columns covered; resets them
+int conflux_lu_debug_panel_phase_stats(unsigned long long *out9) {
+    if (!out9) return CONFLUX_LU_EARG;
+    for (int i = 0; i < 8; ++i) {
+        out9[i] = g_panel_phase_acc[i];
+        g_panel_phase_acc[i] = 0;
+    }
+    out9[8] = g_panel_phase_cols;
+    g_panel_phase_cols = 0;
+    return CONFLUX_LU_OK;
 }
 
 int conflux_lu_debug_getrf(int n, int v, double *panel, int *ipiv_out) {

@@ -246,6 +246,8 @@ __global__ void k_row_move(const double *__restrict__ src, int64_t lds,
 // memset stays valid because epoch >= 1.  The winner's ROW INDEX is payload:
 // it rides in a 17th 16-byte chunk of the block's candidate record.
 #define PANEL_REC (PANEL_NB + 2)  // doubles per candidate record (272 B)
+#define PANEL_GR_IDX (2 * PANEL_NB)     // granule holding the row index
+#define PANEL_GR_REC (2 * PANEL_NB + 2)  // granules per R2 record (528 B)
 struct PanelSync2 {
     alignas(16) unsigned long long key[2][CONFLUX_PANEL_MAX_BLOCKS][2];
     // candidate record: PANEL_NB row values, then one 16-byte chunk whose
@@ -256,6 +258,23 @@ struct PanelSync2 {
     // diagnostics: total key-poll iterations (all blocks, all columns) —
     // read+reset by conflux_panel_spin_stats (CONFLUX_SPIN_STATS=1)
     unsigned long long spin_sum;
+    // ---- drain-free (R2) payload of k_panel_factor_reg: every double of a
+    // candidate row / of the diagonal row travels as two self-validating
+    // granules like the key, (epoch<<32)|hi32 and (epoch<<32)|lo32, each
+    // written by ONE aligned 8-byte relaxed agent-scope store.  Granule
+    // PANEL_GR_IDX of a block's record carries the winner's row index.  The
+    // R1 slabs above stay: k_panel_factor (ragged leaves, mode 0) and the
+    // register leaf's R1 form use them on the same struct within one
+    // factorization, the epoch running on from launch to launch.
+    alignas(16) unsigned long long
+        cand_gr[2][CONFLUX_PANEL_MAX_BLOCKS][PANEL_GR_REC];
+    alignas(16) unsigned long long diag_gr[2][2 * PANEL_NB];
+    // diagnostics of the instrumented instantiations: shader-clock cycles
+    // of wave 0 per column phase (poll wait, poll passed -> pivot and
+    // diagonal row in LDS, barrier -> end of the row update and reduction,
+    // combine -> key posted); [0..3] summed over all blocks, [4..7] block 0
+    // alone.  Read and reset by conflux_panel_phase_read.
+    unsigned long long phase[8];
 };
 
 
@@ -319,6 +338,49 @@ DEVFN void wave_first_max(double &d, int &idx) {
     dpp_fold_first_max<0x143, 0xc>(d, idx);  // row_bcast:31 into rows 2, 3
 }
 
+// instrumented instantiations: one block's four phase totals into the sync
+// struct (lane 0 of wave 0; relaxed agent-scope adds, read by the host after
+// the stream has drained)
+DEVFN void panel_phase_add(PanelSync2 *sync, const unsigned long long (&ph)[4],
+                           bool block0) {
+    for (int i = 0; i < 4; ++i) {
+        (void)__hip_atomic_fetch_add((gu64 *)&sync->phase[i], ph[i],
+                                     RLX_AGENT);
+        if (block0)
+            (void)__hip_atomic_fetch_add((gu64 *)&sync->phase[4 + i], ph[i],
+                                         RLX_AGENT);
+    }
+}
+
+// Value-only edition for reductions whose index IS the lane: the wave's
+// largest value by six DPP folds of one v_max_f64 each, returned uniform;
+// the first lane holding it is then one ballot away, instead of carrying the
+// index through two compares and three selects per fold.  Values are never
+// NaN here either.  All 64 lanes must be active.
+template <int CTRL, int ROW_MASK>
+DEVFN void dpp_fold_max(double &d) {
+    union { double d; int i[2]; } s, o;
+    s.d = d;
+    o.i[0] = __builtin_amdgcn_update_dpp(s.i[0], s.i[0], CTRL, ROW_MASK, 0xf,
+                                         false);
+    o.i[1] = __builtin_amdgcn_update_dpp(s.i[1], s.i[1], CTRL, ROW_MASK, 0xf,
+                                         false);
+    d = fmax(d, o.d);
+}
+DEVFN double wave_max(double d) {
+    dpp_fold_max<0x111, 0xf>(d);
+    dpp_fold_max<0x112, 0xf>(d);
+    dpp_fold_max<0x114, 0xf>(d);
+    dpp_fold_max<0x118, 0xf>(d);
+    dpp_fold_max<0x142, 0xa>(d);
+    dpp_fold_max<0x143, 0xc>(d);
+    union { double d; int i[2]; } s, o;
+    s.d = d;
+    o.i[0] = __builtin_amdgcn_readlane(s.i[0], 63);
+    o.i[1] = __builtin_amdgcn_readlane(s.i[1], 63);
+    return o.d;
+}
+
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 union F64x2Bits {
     double d[2];
@@ -364,9 +426,12 @@ __global__ __launch_bounds__(256) void k_trsm_left_lower_unit32(
 // the slab handshake; the row swap is performed by the OWNING blocks from
 // slab-published rows (no cross-block matrix reads, no write races).
 // ---------------------------------------------------------------------------
-template <int QR, int TPB>  // rows/block = QR*TPB; QR=1 halves the
+template <int QR, int TPB, bool STATS = false>
+                            // rows/block = QR*TPB; QR=1 halves the
                             // per-column local update (1 row/thread);
-                            // TPB=256 gives 67 KB LDS (2 blocks/CU)
+                            // TPB=256 gives 67 KB LDS (2 blocks/CU);
+                            // STATS: wave 0 times the column's phases
+                            // (PanelSync2::phase), default build has none
 __global__ __launch_bounds__(TPB) void k_panel_factor(
     double *__restrict__ panel, int64_t ldp, int m, int nb,
     PanelSync2 *__restrict__ sync, int *__restrict__ ipiv,
@@ -394,6 +459,7 @@ __global__ __launch_bounds__(TPB) void k_panel_factor(
         (void *)sync, (short)0, (int)sizeof(PanelSync2), 0x00020000);
 
     unsigned long long spin_acc = 0;  // key-poll iterations (diagnostics)
+    unsigned long long ph[4] = {0, 0, 0, 0}, pt0 = 0, pt1 = 0, pt2 = 0;
     // give-up bound of the key poll: a broken hand-off must end the kernel
     // in about two seconds (legitimate waits are well under a millisecond).
     // One poll pass costs the two granule loads' round trip to L2 plus the
@@ -542,6 +608,7 @@ __global__ __launch_bounds__(TPB) void k_panel_factor(
         // reduction and arrives with the winner record.  A row-cyclic
         // block layout would need the row back in the key.
         if (tid < 64) {
+            if constexpr (STATS) pt0 = clock64();
             double a_d = -1.0;
             int a_win = 0;
             for (int b = tid; b < nblocks; b += 64) {
@@ -574,6 +641,7 @@ __global__ __launch_bounds__(TPB) void k_panel_factor(
             // lanes >= nblocks still hold the (-1.0, 0) start value, which
             // never replaces a real candidate
             wave_first_max(a_d, a_win);
+            if constexpr (STATS) pt1 = clock64();
             // the polling wave is the loading wave: broadcast the winner and
             // issue the payload loads at once (no LDS round + barrier in
             // between).  The wavefront-scope fence emits no instruction; it
@@ -627,6 +695,8 @@ __global__ __launch_bounds__(TPB) void k_panel_factor(
             }
         }
         __syncthreads();
+        if constexpr (STATS)
+            if (tid < 64) pt2 = clock64();
         const int piv = sh_piv;
         const double pivval = piv_lds[c];
         const bool do_scale = pivval != 0.0;
@@ -665,6 +735,9 @@ __global__ __launch_bounds__(TPB) void k_panel_factor(
         }
         if (c + 1 < nb) reduce_to_partials(namax, narow);
         __syncthreads();
+        unsigned long long pt3 = 0;
+        if constexpr (STATS)
+            if (tid < 64) pt3 = clock64();
         if (c + 1 < nb) {
             // tail-publish column c+1's candidate (values final after the
             // barrier above; the publish overlaps other blocks' update
@@ -674,7 +747,16 @@ __global__ __launch_bounds__(TPB) void k_panel_factor(
             combine_partials(wa, wrow);
             publish_col(c + 1, wa, wrow);
         }
+        if constexpr (STATS)
+            if (tid < 64) {
+                ph[0] += pt1 - pt0;
+                ph[1] += pt2 - pt1;
+                ph[2] += pt3 - pt2;
+                ph[3] += clock64() - pt3;
+            }
     }
+    if constexpr (STATS)
+        if (tid == 0) panel_phase_add(sync, ph, bid == 0);
 
     // write back (plain stores; next kernels see them at the launch boundary)
     for (int q = 0; q < QR; ++q) {
@@ -712,6 +794,490 @@ __global__ __launch_bounds__(TPB) void k_panel_factor(
         if (i < 2 * nb) {
             swap_dst[i] = d;
             swap_src[i] = sv;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// register-resident leaf: k_panel_factor for full 32-column sub-panels with
+// the thread's row held in 32 fp64 registers from load to write-back
+// (CONFLUX_PANEL_REG, default 1; 256 rows per block, one row per thread).
+// Pivots, factors and the swap map are bit for bit k_panel_factor's: the
+// same first-max rule, recip = 1.0 / pivot by IEEE division, l = x * recip,
+// one explicit fma(-l, piv[cc], x) per update.
+//
+// Register arrays need compile-time indices, so the arithmetic of a column
+// is panel_reg_column<C>, reached through a 32-way switch inside the ROLLED
+// column loop; the poll, the reductions and the publication are shared code.
+// LDS holds only what is shared: the pivot row and the diagonal row (read
+// back as uniform broadcast reads, 16 bytes at a time), the per-wave
+// partials, the winner's row and the staging slots of the publication.
+// Block 0's swap map lives in registers of its wave 0 (see below), and the
+// wave reductions are one v_max_f64 per DPP fold plus a ballot (the row, or
+// the block, IS the lane).
+//
+// Publication.  The rows no longer sit in LDS where wave 0 could fetch the
+// block's winner, and the block's winner is known only after the column's
+// second barrier.  So BEFORE that barrier every wave stages its OWN
+// candidate row (the lane that owns the wave's first-max writes its 32
+// registers to stage[wave]), and block 0's lane c+1 stages the next diagonal
+// row (rows 0..31 all live in wave 0 of block 0).  After the barrier wave 0
+// combines the four partials, reads stage[winner's wave] and publishes — so,
+// as in k_panel_factor, EVERY hand-off store of a block is issued by wave 0.
+// Ordering, R1 form (PUBLISH = 0): all payload stores are sc1 stores of one
+// wave, that wave drains (vmcnt(0)), then its lane 0 posts the key; no
+// second storing wave exists, so no cross-wave ordering is needed beyond the
+// barrier that already orders the LDS staging.  R2 form (PUBLISH = 1): the
+// payload travels as self-validating granules (PanelSync2::cand_gr /
+// diag_gr), payload and key are issued back to back with NO drain, and the
+// consumer re-reads its granules until every tag carries the column's epoch
+// (bounded like the key poll; err code 0x10000 + 1 + column).  R2 is not
+// offered for k_panel_factor: it keeps the R1 slabs.
+// Resources (gfx950 code object metadata, PUBLISH 0 / 1): 157 / 165 VGPRs,
+// 1848 B LDS, no scratch, no spilled VGPRs, 22.5 / 23.0 KB of code.  Above 128
+// registers two 256-thread blocks fit a CU: the same 2 blocks per CU and 256
+// rows per block as k_panel_factor's default shape, so
+// conflux_panel_blocks_per_cu() and conflux_panel_rpb() serve both.
+// ---------------------------------------------------------------------------
+#define PANEL_REG_TPB 256
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+
+// column C of one thread's row: scale by the reciprocal and rank-1 update
+// for rows below C.  Only this part indexes the register row by the column,
+// so only this part is instantiated 32 times; the two swap cases are
+// column-independent copies around it (see the column loop).  Returns the
+// value column C+1's candidate is taken from.
+template <int C>
+DEVFN double panel_reg_column(double (&my)[PANEL_NB], const double *piv_lds,
+                              int r) {
+    const double pivval = piv_lds[C];
+    const bool do_scale = pivval != 0.0;
+    const double recip = do_scale ? 1.0 / pivval : 0.0;
+    if (r > C) {
+        const double l = do_scale ? my[C] * recip : my[C];
+        my[C] = l;
+#pragma unroll
+        for (int cc = C + 1; cc < PANEL_NB; ++cc)
+            my[cc] = fma(-l, piv_lds[cc], my[cc]);
+    }
+    if constexpr (C + 1 < PANEL_NB) return my[C + 1];
+    else return 0.0;
+}
+
+template <bool R2, bool STATS>
+__global__ __launch_bounds__(PANEL_REG_TPB) void k_panel_factor_reg(
+    double *__restrict__ panel, int64_t ldp, int m,
+    PanelSync2 *__restrict__ sync, int *__restrict__ ipiv,
+    unsigned int epoch0, int nblocks, int *__restrict__ swap_dst,
+    int *__restrict__ swap_src, int backoff) {
+    constexpr int TPB = PANEL_REG_TPB, NB = PANEL_NB, NW = TPB / 64;
+    const int tid = threadIdx.x, bid = blockIdx.x;
+    const int lane = tid & 63, wv = tid >> 6;
+    const int r = bid * TPB + tid;
+    const bool owns_c = bid == 0 && wv == 0;  // rows 0..31: wave 0, block 0
+    __shared__ alignas(16) double piv_lds[NB];
+    __shared__ alignas(16) double diag_lds[NB];
+    __shared__ alignas(16) double stage[NW][NB];  // each wave's candidate row
+    __shared__ alignas(16) double stage_d[NB];    // block 0: next diag row
+    __shared__ double red_abs[NW];
+    __shared__ int red_row[NW];
+    __shared__ int sh_piv;
+    // the dlaswp row map k_panel_factor composes in LDS with lane 0 walking
+    // the overflow list (one dependent LDS read per entry, on block 0's
+    // critical path between its poll and the block barrier: the r06 phase
+    // split shows block 0 spending 3.4x the other blocks' time there) lives
+    // in REGISTERS of block 0's wave 0 here: lane i holds sm_base[i] and
+    // overflow entry i; the list search is one ballot, every read a
+    // readlane with a uniform index.  Same map, entry for entry.
+    int sm_base_r = tid, sm_opos_r = 0, sm_osrc_r = 0, sm_novf = 0;
+    const auto srsrc = __builtin_amdgcn_make_buffer_rsrc(
+        (void *)sync, (short)0, (int)sizeof(PanelSync2), 0x00020000);
+    unsigned long long spin_acc = 0;
+    unsigned long long ph[4] = {0, 0, 0, 0}, pt0 = 0, pt1 = 0, pt2 = 0;
+    // give-up bound: as in k_panel_factor
+    const unsigned sleep_k =
+        backoff == 1 ? 1u : backoff == 2 ? 2u : backoff >= 4 ? 4u : 0u;
+    const unsigned spin_limit = 2000000000u / (200u + 27u * sleep_k);
+    auto backoff_sleep = [&]() {
+        if (backoff == 1) __builtin_amdgcn_s_sleep(1);
+        else if (backoff == 2) __builtin_amdgcn_s_sleep(2);
+        else if (backoff >= 4) __builtin_amdgcn_s_sleep(4);
+    };
+
+    // ---- load: 16 x 16 bytes, 256 contiguous bytes per row
+    double my[NB];
+    if (r < m) {
+        const f64x2 *src = (const f64x2 *)(panel + (int64_t)r * ldp);
+#pragma unroll
+        for (int k = 0; k < NB / 2; ++k) {
+            const f64x2 t = src[k];
+            my[2 * k] = t.x;
+            my[2 * k + 1] = t.y;
+        }
+    } else {
+#pragma unroll
+        for (int cc = 0; cc < NB; ++cc) my[cc] = 0.0;
+    }
+    auto stage_row = [&](double *dst) {
+#pragma unroll
+        for (int k = 0; k < NB / 2; ++k) {
+            f64x2 t;
+            t.x = my[2 * k];
+            t.y = my[2 * k + 1];
+            ((f64x2 *)dst)[k] = t;
+        }
+    };
+    // per-wave first-max of the threads' candidates (amax = |value|, or
+    // -1.0 without one): rows ascend with the lane, so the first lane that
+    // holds the wave's maximum is the first-max row.  Lane 0 writes the
+    // wave's partial, the lane owning the wave's winner stages its row,
+    // block 0's lane dcol stages the diagonal row dcol
+    auto reduce_and_stage = [&](double amax, int dcol) {
+        const double mx = wave_max(amax);
+        const unsigned long long hit =
+            __builtin_amdgcn_ballot_w64(amax == mx);
+        const int wrow_w = mx > -1.0
+                               ? bid * TPB + wv * 64 + (int)__builtin_ctzll(hit)
+                               : m;
+        if (lane == 0) {
+            red_abs[wv] = mx;
+            red_row[wv] = wrow_w;
+        }
+        if (wrow_w < m && r == wrow_w) stage_row(stage[wv]);
+        if (owns_c && tid == dcol) stage_row(stage_d);
+    };
+    // wave 0 only, after the barrier that follows reduce_and_stage
+    auto combine_partials = [&](double &wa, int &wrow) {
+        wa = red_abs[0];
+        wrow = red_row[0];
+        for (int w = 1; w < NW; ++w) {
+            const double oa = red_abs[w];
+            const int orr = red_row[w];
+            if (oa > wa || (oa == wa && orr < wrow)) { wa = oa; wrow = orr; }
+        }
+    };
+    // wave 0 only: publish column pc's candidate record (+ block 0: the
+    // diagonal row pc) and post the key.  A block without a candidate
+    // (wa = -1.0) publishes stage[0]'s leftover: it never wins.
+    auto publish_col = [&](int pc, double wa, int wrow) {
+        const unsigned int pep = epoch0 + (unsigned)pc;
+        const int ppar = (int)(pep & 1u);
+        const int wwave = wrow < m ? (wrow - bid * TPB) >> 6 : 0;
+        const unsigned long long tag = (unsigned long long)pep << 32;
+        union { double d; unsigned long long u; } a;
+        if constexpr (R2) {
+            // lanes 0-31: the two granules of one double of the candidate
+            // row; block 0's lanes 32-63: of the diagonal row.  Each granule
+            // is ONE aligned 8-byte atomic store; no drain before the key.
+            if (tid < 32) {
+                a.d = stage[wwave][tid];
+                unsigned long long *g = &sync->cand_gr[ppar][bid][2 * tid];
+                st_rlx_u64(g, tag | (a.u >> 32));
+                st_rlx_u64(g + 1, tag | (a.u & 0xffffffffull));
+            } else if (bid == 0) {
+                a.d = stage_d[tid - 32];
+                unsigned long long *g = &sync->diag_gr[ppar][2 * (tid - 32)];
+                st_rlx_u64(g, tag | (a.u >> 32));
+                st_rlx_u64(g + 1, tag | (a.u & 0xffffffffull));
+            }
+            if (tid == 0)
+                st_rlx_u64(&sync->cand_gr[ppar][bid][PANEL_GR_IDX],
+                           tag | (unsigned long long)(unsigned)wrow);
+        } else {
+            const int rec_off =
+                (int)offsetof(PanelSync2, cand_row) +
+                (ppar * CONFLUX_PANEL_MAX_BLOCKS + bid) * PANEL_REC * 8;
+            if (tid == 32) {
+                i32x4 rv = {wrow, 0, 0, 0};
+                __builtin_amdgcn_raw_buffer_store_b128(
+                    rv, srsrc, rec_off + NB * 8, 0, /*sc1*/ 16);
+            }
+            if (tid < 16) {
+                F64x2Bits x;
+                x.d[0] = stage[wwave][2 * tid];
+                x.d[1] = stage[wwave][2 * tid + 1];
+                __builtin_amdgcn_raw_buffer_store_b128(
+                    x.v, srsrc, rec_off + 16 * tid, 0, /*sc1*/ 16);
+            } else if (tid < 32 && bid == 0) {
+                const int l = tid - 16;
+                F64x2Bits x;
+                x.d[0] = stage_d[2 * l];
+                x.d[1] = stage_d[2 * l + 1];
+                __builtin_amdgcn_raw_buffer_store_b128(
+                    x.v, srsrc,
+                    (int)offsetof(PanelSync2, diag_row) + ppar * NB * 8 +
+                        16 * l,
+                    0, /*sc1*/ 16);
+            }
+            // R1: the one storing wave drains, then posts the key
+            drain_stores();
+        }
+        if (tid == 0) {
+            a.d = wa;
+            st_rlx_u64(&sync->key[ppar][bid][0], tag | (a.u >> 32));
+            st_rlx_u64(&sync->key[ppar][bid][1], tag | (a.u & 0xffffffffull));
+        }
+    };
+
+    // column 0's candidate; every later one is reduced and published at the
+    // tail of the previous column's update
+    {
+        // (a NaN is never a candidate: the comparison is false for it)
+        double amax = -1.0;
+        if (r < m && fabs(my[0]) > -1.0) amax = fabs(my[0]);
+        reduce_and_stage(amax, 0);
+        __syncthreads();
+        if (tid < 64) {
+            double wa;
+            int wrow;
+            combine_partials(wa, wrow);
+            publish_col(0, wa, wrow);
+        }
+    }
+
+    for (int c = 0; c < NB; ++c) {
+        const unsigned int epoch = epoch0 + (unsigned)c;
+        const int par = (int)(epoch & 1u);
+        // ---- wave 0 of EVERY block: poll all keys, reduce the winner
+        // (lower block wins ties: blocks own ascending row ranges), fetch the
+        // winner's record and the diagonal row into LDS
+        if (tid < 64) {
+            if constexpr (STATS) pt0 = clock64();
+            double a_d = -1.0;
+            int a_win = 0;
+            for (int b = tid; b < nblocks; b += 64) {
+                unsigned long long g0, g1;
+                unsigned spins = 0;
+                for (;;) {
+                    g0 = ld_rlx_u64(&sync->key[par][b][0]);
+                    g1 = ld_rlx_u64(&sync->key[par][b][1]);
+                    if ((unsigned)(g0 >> 32) == epoch &&
+                        (unsigned)(g1 >> 32) == epoch)
+                        break;
+                    backoff_sleep();
+                    if (++spins > spin_limit) {
+                        st_rlx_u32(&sync->err, 1u + (unsigned)c);
+                        break;
+                    }
+                }
+                spin_acc += spins;
+                union { double d; unsigned long long u; } a;
+                a.u = (g0 << 32) | (g1 & 0xffffffffull);
+                if (a.d > a_d) {
+                    a_d = a.d;
+                    a_win = b;
+                }
+            }
+            // up to 64 blocks lane b polled block b alone: first lane with
+            // the largest key; more blocks: the (value, index) fold
+            int win;
+            if (nblocks <= 64) {
+                const double mx = wave_max(a_d);
+                win = (int)__builtin_ctzll(
+                    __builtin_amdgcn_ballot_w64(a_d == mx));
+            } else {
+                wave_first_max(a_d, a_win);
+                win = __builtin_amdgcn_readlane(a_win, 63);
+            }
+            if constexpr (STATS) pt1 = clock64();
+            int w_row;
+            if constexpr (R2) {
+                // lane i: double i of the winner's record, lane 32+i: double
+                // i of the diagonal row, every lane: the row-index granule.
+                // Re-read until every tag is this column's epoch (normally
+                // the first pass: the key was posted after the payload).
+                const unsigned long long *src =
+                    tid < 32 ? &sync->cand_gr[par][win][2 * tid]
+                             : &sync->diag_gr[par][2 * (tid - 32)];
+                const unsigned long long *isrc =
+                    &sync->cand_gr[par][win][PANEL_GR_IDX];
+                unsigned long long g0, g1, gi;
+                unsigned spins = 0;
+                for (;;) {
+                    g0 = ld_rlx_u64(src);
+                    g1 = ld_rlx_u64(src + 1);
+                    gi = ld_rlx_u64(isrc);
+                    const bool stale = (unsigned)(g0 >> 32) != epoch ||
+                                       (unsigned)(g1 >> 32) != epoch ||
+                                       (unsigned)(gi >> 32) != epoch;
+                    if (__builtin_amdgcn_ballot_w64(stale) == 0ull) break;
+                    backoff_sleep();
+                    if (++spins > spin_limit) {
+                        if (tid == 0)
+                            st_rlx_u32(&sync->err,
+                                       0x10000u + 1u + (unsigned)c);
+                        break;
+                    }
+                }
+                spin_acc += tid == 0 ? spins : 0u;
+                union { double d; unsigned long long u; } a;
+                a.u = (g0 << 32) | (g1 & 0xffffffffull);
+                if (tid < 32) piv_lds[tid] = a.d;
+                else diag_lds[tid - 32] = a.d;
+                w_row = __builtin_amdgcn_readfirstlane((int)(unsigned)gi);
+            } else {
+                // R1: sc1 loads behind the poll, as in k_panel_factor
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                i32x4 rec = {0, 0, 0, 0};
+                if (tid <= 16)
+                    rec = __builtin_amdgcn_raw_buffer_load_b128(
+                        srsrc,
+                        (int)offsetof(PanelSync2, cand_row) +
+                            (par * CONFLUX_PANEL_MAX_BLOCKS + win) *
+                                PANEL_REC * 8 +
+                            16 * tid,
+                        0, /*sc1*/ 16);
+                if (tid < 16) {
+                    F64x2Bits x;
+                    x.v = rec;
+                    piv_lds[2 * tid] = x.d[0];
+                    piv_lds[2 * tid + 1] = x.d[1];
+                    x.v = __builtin_amdgcn_raw_buffer_load_b128(
+                        srsrc,
+                        (int)offsetof(PanelSync2, diag_row) + par * NB * 8 +
+                            16 * tid,
+                        0, /*sc1*/ 16);
+                    diag_lds[2 * tid] = x.d[0];
+                    diag_lds[2 * tid + 1] = x.d[1];
+                }
+                w_row = __builtin_amdgcn_readlane(rec[0], 16);
+            }
+            if (tid == 0) {
+                sh_piv = w_row;
+                if (bid == 0) ipiv[c] = w_row;
+            }
+            if (bid == 0) {
+                // compose the swap (c <-> w_row) into the row map; w_row, c,
+                // j and sm_novf are wave-uniform, all 64 lanes are active
+                int bval, j = 0;
+                if (w_row < NB) {
+                    bval = __builtin_amdgcn_readlane(sm_base_r, w_row);
+                } else {
+                    const unsigned long long hit = __builtin_amdgcn_ballot_w64(
+                        tid < sm_novf && sm_opos_r == w_row);
+                    if (hit) {
+                        j = __builtin_ctzll(hit);
+                    } else {
+                        j = sm_novf;
+                        if (tid == j) {
+                            sm_opos_r = w_row;
+                            sm_osrc_r = w_row;
+                        }
+                        ++sm_novf;
+                    }
+                    bval = __builtin_amdgcn_readlane(sm_osrc_r, j);
+                }
+                const int t = __builtin_amdgcn_readlane(sm_base_r, c);
+                if (tid == c) sm_base_r = bval;
+                if (w_row < NB) {
+                    if (tid == w_row) sm_base_r = t;
+                } else if (tid == j) {
+                    sm_osrc_r = t;
+                }
+            }
+        }
+        __syncthreads();
+        if constexpr (STATS)
+            if (tid < 64) pt2 = clock64();
+        const int piv = sh_piv;
+
+        // ---- the column's arithmetic on the register row
+        double nxt = 0.0;
+#define PANEL_REG_CASE(C)                                                     \
+    case C:                                                                   \
+        nxt = panel_reg_column<C>(my, piv_lds, r);                            \
+        break;
+        // the pivot's old row (below c) takes the diagonal row: load it
+        // over the register row and let the normal path scale and update
+        // it — columns below c copied, column c scaled, the rest
+        // fma(-l, piv[cc], diag[cc]), exactly k_panel_factor's r == piv
+        // arithmetic.  One wave per column pays this branch.
+        if (r == piv && r > c) {
+#pragma unroll
+            for (int k = 0; k < NB / 2; ++k) {
+                const f64x2 t = ((const f64x2 *)diag_lds)[k];
+                my[2 * k] = t.x;
+                my[2 * k + 1] = t.y;
+            }
+        }
+        switch (c) {
+            PANEL_REG_CASE(0) PANEL_REG_CASE(1) PANEL_REG_CASE(2)
+            PANEL_REG_CASE(3) PANEL_REG_CASE(4) PANEL_REG_CASE(5)
+            PANEL_REG_CASE(6) PANEL_REG_CASE(7) PANEL_REG_CASE(8)
+            PANEL_REG_CASE(9) PANEL_REG_CASE(10) PANEL_REG_CASE(11)
+            PANEL_REG_CASE(12) PANEL_REG_CASE(13) PANEL_REG_CASE(14)
+            PANEL_REG_CASE(15) PANEL_REG_CASE(16) PANEL_REG_CASE(17)
+            PANEL_REG_CASE(18) PANEL_REG_CASE(19) PANEL_REG_CASE(20)
+            PANEL_REG_CASE(21) PANEL_REG_CASE(22) PANEL_REG_CASE(23)
+            PANEL_REG_CASE(24) PANEL_REG_CASE(25) PANEL_REG_CASE(26)
+            PANEL_REG_CASE(27) PANEL_REG_CASE(28) PANEL_REG_CASE(29)
+            PANEL_REG_CASE(30) PANEL_REG_CASE(31)
+        }
+#undef PANEL_REG_CASE
+        // row c takes the pivot row in all 32 columns: a select, and only in
+        // the wave that holds rows 0..31 (a wave-uniform branch)
+        if (owns_c) {
+            const bool is_c = r == c;
+#pragma unroll
+            for (int cc = 0; cc < NB; ++cc)
+                my[cc] = is_c ? piv_lds[cc] : my[cc];
+        }
+        // candidates for column c+1 are exactly the rows updated above
+        if (c + 1 < NB) {
+            double namax = -1.0;
+            if (r > c && r < m && fabs(nxt) > -1.0) namax = fabs(nxt);
+            reduce_and_stage(namax, c + 1);
+        }
+        __syncthreads();
+        unsigned long long pt3 = 0;
+        if constexpr (STATS)
+            if (tid < 64) pt3 = clock64();
+        if (c + 1 < NB && tid < 64) {
+            double wa;
+            int wrow;
+            combine_partials(wa, wrow);
+            publish_col(c + 1, wa, wrow);
+        }
+        if constexpr (STATS)
+            if (tid < 64) {
+                ph[0] += pt1 - pt0;
+                ph[1] += pt2 - pt1;
+                ph[2] += pt3 - pt2;
+                ph[3] += clock64() - pt3;
+            }
+    }
+    if constexpr (STATS)
+        if (tid == 0) panel_phase_add(sync, ph, bid == 0);
+
+    // ---- write back: 16 x 16 bytes per row
+    if (r < m) {
+        f64x2 *dst = (f64x2 *)(panel + (int64_t)r * ldp);
+#pragma unroll
+        for (int k = 0; k < NB / 2; ++k) {
+            f64x2 t;
+            t.x = my[2 * k];
+            t.y = my[2 * k + 1];
+            dst[k] = t;
+        }
+    }
+    if (tid < 64) {
+        unsigned long long t = spin_acc;
+        for (int w2 = 32; w2 > 0; w2 >>= 1) t += __shfl_down(t, w2);
+        if (tid == 0 && t)
+            (void)__hip_atomic_fetch_add((gu64 *)&sync->spin_sum, t,
+                                         RLX_AGENT);
+    }
+    // block 0: emit the composed row-permutation map in k_panel_factor's
+    // layout (identity-padded by duplicating entry 0): lane k writes entry k
+    // and overflow entry k
+    if (bid == 0 && tid < 64 && swap_dst) {
+        const int base0 = __builtin_amdgcn_readlane(sm_base_r, 0);
+        if (tid < NB) {
+            const bool used = tid < sm_novf;
+            swap_dst[tid] = tid;
+            swap_src[tid] = sm_base_r;
+            swap_dst[NB + tid] = used ? sm_opos_r : 0;
+            swap_src[NB + tid] = used ? sm_osrc_r : base0;
         }
     }
 }
@@ -1921,6 +2487,49 @@ static void panel_shape(int *qr, int *tpb) {
     *tpb = g_tpb;
 }
 
+// Leaf-kernel switches, process-global like the glue switch of the engine;
+// each setter returns the previous mode.
+//   CONFLUX_PANEL_REG (default 1): full 32-column leaves run the
+//     register-resident k_panel_factor_reg; 0 = k_panel_factor everywhere.
+//   CONFLUX_PANEL_PUBLISH (default 0): hand-off form of the register leaf,
+//     1 = drain-free granule payload (R2), 0 = sc1 payload + drain + key.
+//     R2 is 4 % faster on the sequential panel but did not pass the A/B
+//     rule under the concurrent trailing GEMM (profiles/r06_panel_ab.log).
+//   CONFLUX_PANEL_PHASE_STATS (default 0): run the instrumented
+//     instantiations that time the phases of a column.
+static int g_panel_reg = -1, g_panel_publish = -1, g_panel_phase = -1;
+static int env_mode(int &g, const char *name, int dflt) {
+    if (g < 0) {
+        const char *e = getenv(name);
+        g = e ? (atoi(e) != 0) : dflt;
+    }
+    return g;
+}
+int conflux_panel_reg_mode() {
+    return env_mode(g_panel_reg, "CONFLUX_PANEL_REG", 1);
+}
+int conflux_panel_publish_mode() {
+    return env_mode(g_panel_publish, "CONFLUX_PANEL_PUBLISH", 0);
+}
+int conflux_panel_phase_stats_mode() {
+    return env_mode(g_panel_phase, "CONFLUX_PANEL_PHASE_STATS", 0);
+}
+int conflux_panel_set_reg_mode(int mode) {
+    const int prev = conflux_panel_reg_mode();
+    g_panel_reg = mode != 0;
+    return prev;
+}
+int conflux_panel_set_publish_mode(int mode) {
+    const int prev = conflux_panel_publish_mode();
+    g_panel_publish = mode != 0;
+    return prev;
+}
+int conflux_panel_set_phase_stats_mode(int mode) {
+    const int prev = conflux_panel_phase_stats_mode();
+    g_panel_phase = mode != 0;
+    return prev;
+}
+
 static int panel_qr() {
     int qr, tpb;
     panel_shape(&qr, &tpb);
@@ -1955,6 +2564,38 @@ int launch_panel_factor(double *panel, int64_t ldp, int m, int nb, void *sync,
         nblocks = (int)cdiv64(m, rpb);
     }
     if (nblocks > CONFLUX_PANEL_MAX_BLOCKS) return -1;  // not resident: refuse
+    const int stats = conflux_panel_phase_stats_mode();
+    // register-resident leaf: full 32-column leaves at the default 256x256
+    // shape whose rows are 16-byte aligned (its loads and stores are 16
+    // bytes wide).  Same rows per block and the same 2 blocks per CU as the
+    // LDS kernel at that shape, so conflux_panel_rpb() and
+    // conflux_panel_blocks_per_cu() hold for both and the refusal above is
+    // the same.
+    if (conflux_panel_reg_mode() && nb == PANEL_NB && m >= PANEL_NB &&
+        qr == 1 &&
+        tpb == PANEL_REG_TPB && ldp % 2 == 0 &&
+        ((uintptr_t)panel & 15u) == 0) {
+        const int r2 = conflux_panel_publish_mode();
+#define PANEL_REG_LAUNCH(R2, ST)                                              \
+    hipLaunchKernelGGL((k_panel_factor_reg<R2, ST>), dim3(nblocks),           \
+                       dim3(PANEL_REG_TPB), 0, s, panel, ldp, m,              \
+                       (PanelSync2 *)sync, ipiv, epoch0, nblocks, swap_dst,   \
+                       swap_src, backoff)
+        if (r2 && stats) PANEL_REG_LAUNCH(true, true);
+        else if (r2) PANEL_REG_LAUNCH(true, false);
+        else if (stats) PANEL_REG_LAUNCH(false, true);
+        else PANEL_REG_LAUNCH(false, false);
+#undef PANEL_REG_LAUNCH
+        return 0;
+    }
+    if (stats && qr == 1 && tpb == 256) {
+        // instrumented build of the default-shape LDS kernel
+        hipLaunchKernelGGL((k_panel_factor<1, 256, true>), dim3(nblocks),
+                           dim3(256), 0, s, panel, ldp, m, nb,
+                           (PanelSync2 *)sync, ipiv, epoch0, nblocks,
+                           swap_dst, swap_src, backoff);
+        return 0;
+    }
     if (qr == 1 && tpb == 512)
         hipLaunchKernelGGL((k_panel_factor<1, 512>), dim3(nblocks), dim3(512),
                            0, s, panel, ldp, m, nb, (PanelSync2 *)sync, ipiv,
@@ -1981,6 +2622,15 @@ void conflux_panel_spin_read(void *sync, unsigned long long *out,
     (void)hipStreamSynchronize(s);
     (void)hipMemsetAsync((char *)sync + offsetof(PanelSync2, spin_sum), 0, 8,
                          s);
+}
+
+// the eight phase totals (PanelSync2::phase), read and reset like spin_sum
+void conflux_panel_phase_read(void *sync, unsigned long long *out8,
+                              hipStream_t s) {
+    char *p = (char *)sync + offsetof(PanelSync2, phase);
+    (void)hipMemcpyAsync(out8, p, 64, hipMemcpyDeviceToHost, s);
+    (void)hipStreamSynchronize(s);
+    (void)hipMemsetAsync(p, 0, 64, s);
 }
 
 int conflux_panel_sync_bytes() { return (int)sizeof(PanelSync2); }

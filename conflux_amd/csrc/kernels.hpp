@@ -44,6 +44,18 @@ int conflux_panel_sync_bytes();
 int conflux_panel_err_offset();  // byte offset of the give-up word (u32)
 void conflux_panel_spin_read(void *sync, unsigned long long *out,
                              hipStream_t s);
+// leaf-kernel switches (CONFLUX_PANEL_REG / _PUBLISH / _PHASE_STATS); the
+// setters return the previous mode.  phase_read: the eight cycle totals of
+// the instrumented kernels (four phases summed over all blocks, then block
+// 0's), read and reset.
+int conflux_panel_reg_mode();
+int conflux_panel_publish_mode();
+int conflux_panel_phase_stats_mode();
+int conflux_panel_set_reg_mode(int mode);
+int conflux_panel_set_publish_mode(int mode);
+int conflux_panel_set_phase_stats_mode(int mode);
+void conflux_panel_phase_read(void *sync, unsigned long long *out8,
+                              hipStream_t s);
 int conflux_panel_nb();
 int conflux_panel_rpb();
 int conflux_panel_blocks_per_cu();
