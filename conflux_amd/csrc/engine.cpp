@@ -1340,19 +1340,27 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
     // degenerate 1-rank grid: solve the v columns step k+1's panel needs
     // FIRST and record ev_t5a after them, so the (a) GEMM and the next
     // panel chain start without waiting for the rest of the A01 solve.
-    // MEASURED ABLATION (r02, default OFF): bit-identical and parity-green
-    // but SLOWER — 229.6 vs 201 ms/step at N=16384.  The fused TRSM
-    // streams all previously-solved 32-wide L panels through LDS once PER
-    // LAUNCH regardless of the X width, so the 3-way column split nearly
-    // triples the solve cost (trsm 33 -> 65 ms/job) and eats the overlap
-    // gain.  Would need a width-proportional TRSM to pay.
+    // HISTORY: off by default from r02 to r06.  With r02's fused TRSM, which
+    // streamed all previously-solved 32-wide L panels through LDS once PER
+    // LAUNCH whatever the X width, the split nearly tripled the solve cost
+    // (trsm 33 -> 65 ms/job) and the step was slower (229.6 vs 201 ms at
+    // N=16384).  The r05 stripe solves are width-proportional: re-measured in
+    // r07 (profiles/r07_leaf_body_ab.log) the split costs 7 ms of solve time
+    // (trsm 22.5 -> 29.5 ms/job) and the step is 5-6 ms FASTER in every
+    // alternated pair, so it is on by default (CONFLUX_SLICE_TRSM=0 turns
+    // it off).  Same pivots either way.
     static int slice_env = -1;
     if (slice_env < 0) {
         const char *se2 = getenv("CONFLUX_SLICE_TRSM");
-        slice_env = se2 ? atoi(se2) : 0;
+        slice_env = se2 ? atoi(se2) : 1;
     }
+    // (only where the next panel runs concurrently, the condition of
+    // async_look below: in sequential mode, CONFLUX_LOOKAHEAD=0, nothing
+    // waits for the slice and the split costs its 7 ms for nothing)
+    const char *lk_slice = getenv("CONFLUX_LOOKAHEAD");
     const bool slice_first =
-        split_trsm && slice_env && Pz == 1 && Px == 1 && look;
+        split_trsm && slice_env && Pz == 1 && Px == 1 && look &&
+        c.panel_stream && (lk_slice ? atoi(lk_slice) != 0 : true);
     // store_factors: the solved U rows (and the diagonal tile) go to Fres,
     // on whichever stream the solve ran
     auto store_u = [&](RankState &r) {

@@ -834,7 +834,7 @@ __global__ __launch_bounds__(TPB) void k_panel_factor(
 // (bounded like the key poll; err code 0x10000 + 1 + column).  R2 is not
 // offered for k_panel_factor: it keeps the R1 slabs.
 // Resources (gfx950 code object metadata, PUBLISH 0 / 1): 157 / 165 VGPRs,
-// 1848 B LDS, no scratch, no spilled VGPRs, 22.5 / 23.0 KB of code.  Above 128
+// 1848 B LDS, no scratch, no spilled VGPRs, 22.9 / 23.4 KB of code.  Above 128
 // registers two 256-thread blocks fit a CU: the same 2 blocks per CU and 256
 // rows per block as k_panel_factor's default shape, so
 // conflux_panel_blocks_per_cu() and conflux_panel_rpb() serve both.
@@ -944,6 +944,13 @@ __global__ __launch_bounds__(PANEL_REG_TPB) void k_panel_factor_reg(
             red_row[wv] = wrow_w;
         }
         if (wrow_w < m && r == wrow_w) stage_row(stage[wv]);
+        // A block without any candidate publishes stage[0]; it wins only
+        // when NO block has one (every remaining entry of the column is a
+        // NaN).  k_panel_factor publishes the block's first row as it stands
+        // then, so a wave 0 without a candidate stages that row: the two
+        // kernels return the same bits on such input too.  Ordinary data
+        // never takes this branch.
+        if (wv == 0 && wrow_w >= m && lane == 0) stage_row(stage[0]);
         if (owns_c && tid == dcol) stage_row(stage_d);
     };
     // wave 0 only, after the barrier that follows reduce_and_stage
@@ -958,7 +965,8 @@ __global__ __launch_bounds__(PANEL_REG_TPB) void k_panel_factor_reg(
     };
     // wave 0 only: publish column pc's candidate record (+ block 0: the
     // diagonal row pc) and post the key.  A block without a candidate
-    // (wa = -1.0) publishes stage[0]'s leftover: it never wins.
+    // (wa = -1.0) publishes stage[0], its first row (see reduce_and_stage):
+    // it wins only when no block has a candidate.
     auto publish_col = [&](int pc, double wa, int wrow) {
         const unsigned int pep = epoch0 + (unsigned)pc;
         const int ppar = (int)(pep & 1u);
