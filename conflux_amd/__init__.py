@@ -70,6 +70,11 @@ def _load():
         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong,
         ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p,
         ctypes.c_void_p]
+    lib.conflux_lu_debug_set_one_rank_direct.argtypes = [ctypes.c_int]
+    lib.conflux_lu_debug_trsm_oop.argtypes = [
+        ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong,
+        ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.conflux_lu_debug_dgemm_bench.argtypes = [
         ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
         ctypes.POINTER(ctypes.c_double)]

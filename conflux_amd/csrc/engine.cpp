@@ -138,6 +138,8 @@ struct Ctx {
     std::vector<RankState> rs;   // size P (sim) or 1 (distributed)
     std::vector<int> pivotInds;  // M, global pivot ids (all ranks identical)
     unsigned epoch = 1;
+    int direct = 0;              // one-rank direct bits of the factorization
+                                 // in flight (ORD_*, set by factor_loop)
     std::vector<EvPair> evs;
     size_t evs_used = 0;
     TimeCat cats[4];
@@ -465,10 +467,13 @@ int trsm_stripe_mode() {
 
 // the stripe solves' scratch (block-major copy of the triangle): slot 0 for
 // the right solve, slot 1 for the left solve, which may run concurrently
-int stripe_ws(RankState &r, int v, int which, double **ws) {
+// which: 0 = the right solve's triangle, 1 = the left solve's; set: the
+// one-rank direct path packs step k's pair into set k & 1 while step k-1's
+// left solve may still read the other
+int stripe_ws(RankState &r, int v, int which, double **ws, int set = 0) {
     const int64_t n = conflux_trsm_stripe_ws_doubles(v);
-    if (!r.triws) HIPCHK(hipMalloc(&r.triws, 2 * n * 8));
-    *ws = r.triws + which * n;
+    if (!r.triws) HIPCHK(hipMalloc(&r.triws, 4 * n * 8));
+    *ws = r.triws + (2 * set + which) * n;
     return 0;
 }
 
@@ -496,6 +501,71 @@ int fused_trsm_left(RankState &r, double *X, int64_t ldx, int v, int64_t N,
 }
 
 // blocked TRSMs on full panels (diag blocks of PANEL_NB + MFMA updates) -----
+// ---------------------------------------------------------------------------
+// CONFLUX_ONE_RANK_DIRECT: on the one-rank grid (one process, Px = Py = Pz =
+// 1, not simulated) the step between two panel chains need not mirror the
+// distributed exchanges.  A bit mask, default 7, process-global;
+// conflux_lu_debug_set_one_rank_direct overrides it:
+//   1  the panel solves read A11 and write A10Rcv / A01Rcv directly, the
+//      panel input is one copy, each triangle is packed once per step
+//   2  the row push of A11 covers only the 2v columns the next panel chain
+//      needs before the solves start; the rest follows on the solve stream
+//   4  the column block of the panel just factored is neither solved for nor
+//      updated (no later step reads it)
+// 0 keeps the staged path of the distributed grids: the A/B baseline and the
+// bitwise reference of tests/test_one_rank_direct_gpu.py.  No bit changes a
+// floating-point operation on an element that is read afterwards.
+enum { ORD_SOLVES = 1, ORD_PUSH = 2, ORD_DEAD = 4, ORD_ALL = 7 };
+int g_one_rank_direct = -1;
+int one_rank_direct_mode() {
+    if (g_one_rank_direct < 0) {
+        const char *e = getenv("CONFLUX_ONE_RANK_DIRECT");
+        g_one_rank_direct = e ? (atoi(e) & ORD_ALL) : ORD_ALL;
+    }
+    return g_one_rank_direct;
+}
+// the bits in force on this engine; bit 1 needs the stripe solves
+int one_rank_direct_bits(const Ctx &c) {
+    if (c.sim || c.world != 1 || c.Px != 1 || c.Py != 1 || c.Pz != 1) return 0;
+    int bits = one_rank_direct_mode();
+    if (!(trsm_stripe_mode() && conflux_trsm_stripe_fits(c.v)))
+        bits &= ~ORD_SOLVES;
+    return bits;
+}
+
+// direct path: pack both triangles of A00 for step k (on c.stream, where A00
+// was just written)
+int pack_step_triangles(Ctx &c, RankState &r, int k) {
+    double *wsu, *wsl;
+    if (stripe_ws(r, c.v, 0, &wsu, k & 1) || stripe_ws(r, c.v, 1, &wsl, k & 1))
+        return CONFLUX_LU_EHIP;
+    launch_trsm_pack_tri(r.A00, c.v, c.v, 0, 0, wsu, c.stream);
+    launch_trsm_pack_tri(r.A00, c.v, c.v, 1, 0, wsl, c.stream);
+    return 0;
+}
+
+// direct path: Xd (M x v) <- Xs * U^-1 / Xd (v x N) <- L^-1 * Xs with step
+// k's packed triangles; Xs is only read
+int trsm_right_direct(Ctx &c, RankState &r, int k, const double *Xs,
+                      int64_t lds, double *Xd, int64_t ldd, int64_t M) {
+    double *ws;
+    size_t slot;
+    if (stripe_ws(r, c.v, 0, &ws, k & 1) || ev_begin(c, 2, 0, &slot))
+        return CONFLUX_LU_EHIP;
+    launch_trsm_right_stripe_packed(ws, Xs, lds, Xd, ldd, c.v, M, c.stream);
+    return ev_end(c, slot);
+}
+
+int trsm_left_direct(Ctx &c, RankState &r, int k, const double *Xs,
+                     int64_t lds, double *Xd, int64_t ldd, int64_t N) {
+    double *ws;
+    size_t slot;
+    if (stripe_ws(r, c.v, 1, &ws, k & 1) || ev_begin(c, 2, 0, &slot))
+        return CONFLUX_LU_EHIP;
+    launch_trsm_left_stripe_packed(ws, Xs, lds, Xd, ldd, c.v, N, c.stream);
+    return ev_end(c, slot);
+}
+
 int trsm_right_upper(Ctx &c, RankState &r, double *X, int64_t ldx, int M) {
     const int v = c.v, NB = conflux_panel_nb();
     size_t slot;
@@ -834,6 +904,7 @@ int factor_loop(Ctx &c, double *elapsed_ms) {
     c.evs_used = 0;
     for (auto &t : c.cats) t = TimeCat{};
     g_gap = GapStats{};
+    c.direct = one_rank_direct_bits(c);
 
     int rc = timed_region(c, elapsed_ms, [&]() -> int {
         StepPlan sp;
@@ -886,13 +957,18 @@ int phase01(Ctx &c, int k, StepPlan &sp) {
     const int kcol = k % Py, krow = k % Px;
     const int n_rounds = Px > 1 ? (int)std::ceil(std::log2((double)Px)) : 0;
 
+    // one-rank direct: the column block goes straight into the panel and A10
+    // is not written (its only readers are the push, the right solve and the
+    // slab spread of the staged path)
+    const bool direct = c.direct & ORD_SOLVES;
+
     // ---- step 0: copy active col block to A10, depth-reduce (C1) ----------
     for (auto &r : c.rs) {
-        if (r.pj != kcol) continue;
+        if (r.pj != kcol || direct) continue;
         launch_copy2d(r.A11 + i64(r.fnp) * Nl + loff, Nl,
                       r.A10 + i64(r.fnp) * v, v, r.nact, v, c.stream);
     }
-    {
+    if (!direct) {
         // the panel chain's comm (it may overlap main-stream exchanges);
         // fnp/nact are the same on every rank of a rank row
         std::vector<ReduceItem> items;
@@ -912,7 +988,12 @@ int phase01(Ctx &c, int k, StepPlan &sp) {
         if (r.pj != kcol || r.pk != 0) continue;
         const int n = r.nact;
         // big LUP on the reduced column panel (conflux_opt.hpp:727)
-        launch_copy2d(r.A10 + i64(r.fnp) * v, v, r.panel, v, n, v, c.stream);
+        if (direct)
+            launch_copy2d(r.A11 + i64(r.fnp) * Nl + loff, Nl, r.panel, v, n, v,
+                          c.stream);
+        else
+            launch_copy2d(r.A10 + i64(r.fnp) * v, v, r.panel, v, n, v,
+                          c.stream);
         std::vector<int> ipiv;
         if (n > 0) {
             if (factor_panel(c, r, n, ipiv)) return CONFLUX_LU_EINTERNAL;
@@ -945,6 +1026,7 @@ int phase01(Ctx &c, int k, StepPlan &sp) {
             // Px == 1 (reference gap; intent): A00 = top v x v of factors,
             // gpivots = candidate col 0 gathered by perm — all host-side
             launch_copy2d(r.panel, v, r.A00, v, std::min(v, n), v, c.stream);
+            if (direct && pack_step_triangles(c, r, k)) return CONFLUX_LU_EHIP;
             for (int i = 0; i < v; ++i)
                 sp.gpivots[i] = (perm[i] < n) ? r.gri[r.fnp + perm[i]] : 0;
             if (!c.sim && c.world > 1)  // feed the C4 broadcast below
@@ -1098,6 +1180,65 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
     GapClock::time_point gap_t0;
     if (gap_on) gap_t0 = GapClock::now();
 
+    // the two panel solves run on two streams (steps 4 & 5 below); decided
+    // here because the one-rank direct path shapes its row push by it
+    static int split_env = -1;
+    if (split_env < 0) {
+        const char *se = getenv("CONFLUX_SPLIT_TRSM");
+        split_env = se ? atoi(se) : 1;
+    }
+    const bool split_trsm = !c.sim && c.trsm_stream && split_env;
+    // degenerate 1-rank grid: solve the v columns step k+1's panel needs
+    // FIRST and record ev_t5a after them, so the (a) GEMM and the next
+    // panel chain start without waiting for the rest of the A01 solve.
+    // HISTORY: off by default from r02 to r06.  With r02's fused TRSM, which
+    // streamed all previously-solved 32-wide L panels through LDS once PER
+    // LAUNCH whatever the X width, the split nearly tripled the solve cost
+    // (trsm 33 -> 65 ms/job) and the step was slower (229.6 vs 201 ms at
+    // N=16384).  The r05 stripe solves are width-proportional: re-measured in
+    // r07 (profiles/r07_leaf_body_ab.log) the split costs 7 ms of solve time
+    // (trsm 22.5 -> 29.5 ms/job) and the step is 5-6 ms FASTER in every
+    // alternated pair, so it is on by default (CONFLUX_SLICE_TRSM=0 turns
+    // it off).  Same pivots either way.
+    static int slice_env = -1;
+    if (slice_env < 0) {
+        const char *se2 = getenv("CONFLUX_SLICE_TRSM");
+        slice_env = se2 ? atoi(se2) : 1;
+    }
+    // (only where the next panel runs concurrently, the condition of
+    // async_look below: in sequential mode, CONFLUX_LOOKAHEAD=0, nothing
+    // waits for the slice and the split costs its 7 ms for nothing)
+    const char *lk_slice = getenv("CONFLUX_LOOKAHEAD");
+    const bool slice_first =
+        split_trsm && slice_env && Pz == 1 && Px == 1 && look &&
+        c.panel_stream && (lk_slice ? atoi(lk_slice) != 0 : true);
+    // one-rank direct path (c.direct, see one_rank_direct_mode): direct =
+    // the solves read A11 and write the Rcv buffers, nothing is staged in
+    // A10 / A01pack / A01; sliced = only columns [loff, lnext + v) of A11 are
+    // pushed before ev_t3, the rest on the solve stream behind the slice
+    // solve; dead = the panel's own column block [loff, loff + v) is neither
+    // solved for nor updated.  Stream and hazard argument: DESIGN.md section 1.
+    const bool direct = c.direct & ORD_SOLVES;
+    const bool sliced = (c.direct & ORD_PUSH) && slice_first;
+    const int64_t dead = (c.direct & ORD_DEAD) ? v : 0;
+    const int64_t wfirst = sliced ? lnext + v - loff : wA01;  // before ev_t3
+    // rows that move, one column window [col0, col0 + cols) of mat at a
+    // time: pivot rows to rowtmp, early rows down to the late positions,
+    // pivot rows to [f, f + cnt) (d_idx as uploaded below)
+    auto push_rows = [&](RankState &r, double *mat, int64_t ld, int64_t col0,
+                         int64_t cols, int f, int cnt, int n_early) -> int {
+        size_t slot;
+        if (ev_begin(c, 3, 0, &slot)) return CONFLUX_LU_EHIP;
+        launch_row_gather(mat + col0, ld, r.rowtmp, cols, r.d_idx, cnt, cols,
+                          c.stream);
+        launch_row_move(mat + col0, ld, mat + col0, ld, r.d_idx + v,
+                        r.d_idx + 2 * v, n_early, cols, c.stream);
+        launch_copy2d(r.rowtmp, cols, mat + i64(f) * ld + col0, ld, cnt, cols,
+                      c.stream);
+        return ev_end(c, slot);
+    };
+    int n_early0 = 0;  // rank 0's count, for the sliced push's second part
+
     // ---- step 2: push pivot rows up, pack, depth-reduce (C7) --------------
     for (auto &r : c.rs) {
         const auto &lr = sp.lrows[r.pi];
@@ -1149,20 +1290,17 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
         if (cnt)
             HIPCHK(hipMemcpyAsync(r.d_idx, stage, size_t(4) * v * 4,
                                   hipMemcpyHostToDevice, c.stream));
-        auto push = [&](double *mat, int64_t ld, int64_t cols) -> int {
-            size_t slot;
-            if (ev_begin(c, 3, 0, &slot)) return CONFLUX_LU_EHIP;
-            launch_row_gather(mat, ld, r.rowtmp, cols, r.d_idx, cnt, cols,
-                              c.stream);
-            launch_row_move(mat, ld, mat, ld, r.d_idx + v, r.d_idx + 2 * v,
-                            n_early, cols, c.stream);
-            launch_copy2d(r.rowtmp, cols, mat + i64(f) * ld, ld, cnt, cols,
-                          c.stream);
-            return ev_end(c, slot);
+        auto push = [&](double *mat, int64_t ld, int64_t col0,
+                        int64_t cols) -> int {
+            return push_rows(r, mat, ld, col0, cols, f, cnt, n_early);
         };
-        if (push(r.A11, Nl, Nl)) return CONFLUX_LU_EHIP;
-        if (push(r.A10, v, v)) return CONFLUX_LU_EHIP;
-        if (c.store_factors && push(r.A10hist, Nl, Nl)) return CONFLUX_LU_EHIP;
+        n_early0 = n_early;
+        // (sliced: columns left of loff are not read again)
+        if (sliced ? push(r.A11, Nl, loff, wfirst) : push(r.A11, Nl, 0, Nl))
+            return CONFLUX_LU_EHIP;
+        if (!direct && push(r.A10, v, 0, v)) return CONFLUX_LU_EHIP;
+        if (c.store_factors && push(r.A10hist, Nl, 0, Nl))
+            return CONFLUX_LU_EHIP;
         // host gri/igri update (identical shuffle)
         {
             GapClock::time_point gri_t0;
@@ -1191,8 +1329,9 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
         r.fnp += cnt;
         r.nact -= cnt;
         // pack pivot rows cols loff.. for the depth reduce
-        launch_copy2d(r.A11 + i64(f) * Nl + loff, Nl, r.A01pack, wA01, cnt,
-                      wA01, c.stream);
+        if (!direct)
+            launch_copy2d(r.A11 + i64(f) * Nl + loff, Nl, r.A01pack, wA01, cnt,
+                          wfirst, c.stream);
     }
     {
         std::vector<ReduceItem> items;
@@ -1204,7 +1343,9 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
     }
 
     // ---- step 3: route packed pivot rows to row krow, pivot-ordered (C5/C6)
-    if (!c.sim) {
+    if (direct) {
+        // the left solve reads the pivot rows where the push left them
+    } else if (!c.sim) {
         RankState &me = c.rs[0];
         if (me.pk == 0) {
             NCCLCHK(ncclGroupStart());
@@ -1235,7 +1376,7 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
                                           sp.order[krow].data(), cnt_own * 4,
                                           hipMemcpyHostToDevice, c.stream));
                     launch_row_scatter(me.A01pack, wA01, me.A01, wA01,
-                                       me.d_idx + 3 * v, cnt_own, wA01,
+                                       me.d_idx + 3 * v, cnt_own, wfirst,
                                        c.stream);
                 }
                 int64_t off = 0;
@@ -1294,12 +1435,18 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
                     RankState &me = c.rs[0];
                     if (src && src->grank == me.grank && dst &&
                         dst->grank == me.grank) {
-                        HIPCHK(hipMemcpyAsync(me.d_idx + 2 * v,
-                                              sp.order[pi].data(), cnt * 4,
-                                              hipMemcpyHostToDevice, c.stream));
+                        // (sliced: the second part of the A11 push still
+                        // needs the late list at d_idx + 2v; the order list
+                        // of this one rank row is already at d_idx + 3v)
+                        int *const d_ord = me.d_idx + (sliced ? 3 : 2) * v;
+                        if (!sliced)
+                            HIPCHK(hipMemcpyAsync(d_ord, sp.order[pi].data(),
+                                                  cnt * 4,
+                                                  hipMemcpyHostToDevice,
+                                                  c.stream));
                         launch_row_scatter(me.A10hist + i64(me.fnp - cnt) * Nl,
                                            Nl, me.Fres + i64(ltik) * v * Nl,
-                                           Nl, me.d_idx + 2 * v, cnt, histcols,
+                                           Nl, d_ord, cnt, histcols,
                                            c.stream);
                     } else if (src && src->grank == me.grank) {
                         launch_copy2d(me.A10hist + i64(me.fnp - cnt) * Nl, Nl,
@@ -1331,36 +1478,6 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
     // the step-4 TRSM (the spreads below stay ordered on the main stream,
     // C8 overlapping the step-5 solve like the reference's Iscatterv window,
     // conflux_opt.hpp:1424-1615).
-    static int split_env = -1;
-    if (split_env < 0) {
-        const char *se = getenv("CONFLUX_SPLIT_TRSM");
-        split_env = se ? atoi(se) : 1;
-    }
-    const bool split_trsm = !c.sim && c.trsm_stream && split_env;
-    // degenerate 1-rank grid: solve the v columns step k+1's panel needs
-    // FIRST and record ev_t5a after them, so the (a) GEMM and the next
-    // panel chain start without waiting for the rest of the A01 solve.
-    // HISTORY: off by default from r02 to r06.  With r02's fused TRSM, which
-    // streamed all previously-solved 32-wide L panels through LDS once PER
-    // LAUNCH whatever the X width, the split nearly tripled the solve cost
-    // (trsm 33 -> 65 ms/job) and the step was slower (229.6 vs 201 ms at
-    // N=16384).  The r05 stripe solves are width-proportional: re-measured in
-    // r07 (profiles/r07_leaf_body_ab.log) the split costs 7 ms of solve time
-    // (trsm 22.5 -> 29.5 ms/job) and the step is 5-6 ms FASTER in every
-    // alternated pair, so it is on by default (CONFLUX_SLICE_TRSM=0 turns
-    // it off).  Same pivots either way.
-    static int slice_env = -1;
-    if (slice_env < 0) {
-        const char *se2 = getenv("CONFLUX_SLICE_TRSM");
-        slice_env = se2 ? atoi(se2) : 1;
-    }
-    // (only where the next panel runs concurrently, the condition of
-    // async_look below: in sequential mode, CONFLUX_LOOKAHEAD=0, nothing
-    // waits for the slice and the split costs its 7 ms for nothing)
-    const char *lk_slice = getenv("CONFLUX_LOOKAHEAD");
-    const bool slice_first =
-        split_trsm && slice_env && Pz == 1 && Px == 1 && look &&
-        c.panel_stream && (lk_slice ? atoi(lk_slice) != 0 : true);
     // store_factors: the solved U rows (and the diagonal tile) go to Fres,
     // on whichever stream the solve ran
     auto store_u = [&](RankState &r) {
@@ -1370,12 +1487,51 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
         // global tile >= k; columns left of it carry stale already-factored
         // data the reference never reads (cf. oracle lu_oracle.py step-5
         // `gcs >= off` mask)
-        const int64_t ustart = i64(v) * (r.pj < kcol ? k / Py + 1 : k / Py);
-        if (Nl - ustart > 0)
+        // (dead: the diagonal tile's columns were not solved for; A00 below)
+        const int64_t ustart =
+            i64(v) * (r.pj < kcol ? k / Py + 1 : k / Py) + dead;
+        if (Nl - ustart > 0 && direct)
+            launch_copy2d(r.A01Rcv + (ustart - loff), Nl, Frow + ustart, Nl, v,
+                          Nl - ustart, c.stream);
+        else if (Nl - ustart > 0)
             launch_copy2d(r.A01 + (ustart - loff), wA01, Frow + ustart, Nl, v,
                           Nl - ustart, c.stream);
         if (r.pj == kcol)  // diagonal tile: packed LU from A00
             launch_copy2d(r.A00, v, Frow + loff, Nl, v, v, c.stream);
+    };
+    // step-5 solve of columns [loff + c0, loff + c0 + w): in place in A01, or
+    // direct from the pivot rows in A11 (rows [fnp - v, fnp) after the push)
+    // into A01Rcv
+    auto solve_left = [&](RankState &r, int64_t c0, int64_t w) -> int {
+        if (w <= 0) return 0;
+        if (direct)
+            return trsm_left_direct(c, r, k,
+                                    r.A11 + i64(r.fnp - v) * Nl + loff + c0, Nl,
+                                    r.A01Rcv + c0, Nl, w);
+        return trsm_left_lower(c, r, r.A01 + c0, wA01, w);
+    };
+    // slice-first: what follows the slice on the solve stream (c.stream here)
+    auto solve_rest = [&](RankState &r) -> int {
+        const int64_t s0 = lnext - loff;
+        if (sliced) {
+            // the columns the (b) pieces and later steps read
+            const int64_t wrest = Nl - (lnext + v);
+            if (wrest > 0 &&
+                push_rows(r, r.A11, Nl, lnext + v, wrest, r.fnp - v, v,
+                          n_early0))
+                return CONFLUX_LU_EHIP;
+            if (wrest > 0 && !direct) {
+                launch_copy2d(r.A11 + i64(r.fnp - v) * Nl + lnext + v, Nl,
+                              r.A01pack + wfirst, wA01, v, wrest, c.stream);
+                launch_row_scatter(r.A01pack + wfirst, wA01, r.A01 + wfirst,
+                                   wA01, r.d_idx + 3 * v, v, wrest, c.stream);
+            }
+        }
+        if (dead < s0 && solve_left(r, dead, s0 - dead))
+            return CONFLUX_LU_EINTERNAL;
+        if (solve_left(r, s0 + v, wA01 - s0 - v)) return CONFLUX_LU_EINTERNAL;
+        store_u(r);
+        return 0;
     };
     if (gap_on) {
         g_gap.to_trsm += gap_ms(gap_t0, GapClock::now());
@@ -1388,22 +1544,23 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
         c.stream = c.trsm_stream;
         for (auto &r : c.rs) {
             if (r.pi != krow || r.pk != 0) continue;
-            if (slice_first) {
-                const int64_t s0 = lnext - loff;  // slice start in A01
-                if (trsm_left_lower(c, r, r.A01 + s0, wA01, v))
+            if (!slice_first) {
+                if (solve_left(r, dead, wA01 - dead))
                     return CONFLUX_LU_EINTERNAL;
-                HIPCHK(hipEventRecord(c.ev_t5a, c.stream));
-                if (s0 > 0 && trsm_left_lower(c, r, r.A01, wA01, s0))
-                    return CONFLUX_LU_EINTERNAL;
-                if (wA01 - s0 - v > 0 &&
-                    trsm_left_lower(c, r, r.A01 + s0 + v, wA01,
-                                    wA01 - s0 - v))
-                    return CONFLUX_LU_EINTERNAL;
-            } else if (trsm_left_lower(c, r, r.A01, wA01, wA01))
-                return CONFLUX_LU_EINTERNAL;
-            store_u(r);
+                store_u(r);
+                continue;
+            }
+            const int64_t s0 = lnext - loff;  // slice start in A01
+            if (solve_left(r, s0, v)) return CONFLUX_LU_EINTERNAL;
+            HIPCHK(hipEventRecord(c.ev_t5a, c.stream));
+            // sliced: the rest is enqueued behind the (a) GEMM below.
+            // Started here, its 32-column blocks (one per CU, the whole LDS)
+            // take the CUs from under (a), which is on the critical path and
+            // then runs 2.5x as long (profiles/r08_gap_after.csv)
+            if (!sliced)
+                if (int rc = solve_rest(r)) return rc;
         }
-        HIPCHK(hipEventRecord(c.ev_t5, c.stream));
+        if (!sliced) HIPCHK(hipEventRecord(c.ev_t5, c.stream));
         c.stream = saved;
     }
 
@@ -1412,6 +1569,21 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
     // ---- step 4: A10 <- A10 U^-1, slab-split, spread (C8) ------------------
     for (auto &r : c.rs) {
         if (r.pj != kcol || r.pk != 0) continue;
+        if (direct) {
+            // source: the panel's column block of A11 below the pivot rows
+            // (what the pushed A10 holds on the staged path), untouched;
+            // destination: the GEMM operand itself, no slab spread
+            nanscan(c, "A00", k, r.A00, i64(v) * v);
+            if (r.nact > 0 &&
+                trsm_right_direct(c, r, k, r.A11 + i64(r.fnp) * Nl + loff, Nl,
+                                  r.A10Rcv, c.nlayr, r.nact))
+                return CONFLUX_LU_EINTERNAL;
+            if (c.store_factors)
+                launch_copy2d(r.A10Rcv, c.nlayr,
+                              r.A10hist + i64(r.fnp) * Nl + loff, Nl, r.nact, v,
+                              c.stream);
+            continue;
+        }
         nanscan(c, "A10.pre", k, r.A10 + i64(r.fnp) * v, i64(r.nact) * v);
         nanscan(c, "A00", k, r.A00, i64(v) * v);
         if (trsm_right_upper(c, r, r.A10 + i64(r.fnp) * v, v, r.nact))
@@ -1422,17 +1594,17 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
                           r.A10hist + i64(r.fnp) * Nl + loff, Nl, r.nact, v,
                           c.stream);
     }
-    if (int rc = spread_col_slabs(
-            c, kcol, [](const RankState &r) { return r.fnp; }))
-        return rc;
+    if (!direct)
+        if (int rc = spread_col_slabs(
+                c, kcol, [](const RankState &r) { return r.fnp; }))
+            return rc;
 
     // ---- step 5: A01 <- L^-1 A01 (already issued on the second stream
     // when split_trsm; the C9 spread below waits for it), spread (C9) -------
     if (!split_trsm) {
         for (auto &r : c.rs) {
             if (r.pi != krow || r.pk != 0) continue;
-            if (trsm_left_lower(c, r, r.A01, wA01, wA01))
-                return CONFLUX_LU_EINTERNAL;
+            if (solve_left(r, dead, wA01 - dead)) return CONFLUX_LU_EINTERNAL;
             store_u(r);
         }
     } else if (!slice_first) {
@@ -1449,10 +1621,12 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
             // (b) trailing pieces that read it
             HIPCHK(hipStreamWaitEvent(c.stream, c.ev_t5a, 0));
             const int64_t s0 = lnext - loff;
-            launch_copy2d(r.A01 + s0, wA01, r.A01Rcv + s0, Nl, c.nlayr, v,
-                          c.stream);
-        } else
-            launch_copy2d(r.A01, wA01, r.A01Rcv, Nl, c.nlayr, wA01, c.stream);
+            if (!direct)
+                launch_copy2d(r.A01 + s0, wA01, r.A01Rcv + s0, Nl, c.nlayr, v,
+                              c.stream);
+        } else if (!direct)
+            launch_copy2d(r.A01 + dead, wA01, r.A01Rcv + dead, Nl, c.nlayr,
+                          wA01 - dead, c.stream);
     } else if (int rc = spread_row_panel(
                    c, krow, [&](int) { return wA01; },
                    [](int) { return int64_t(0); }))
@@ -1539,11 +1713,21 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
     if (slice_first) {
         // rest of the A01 solve feeds the (b) pieces below
         RankState &r = c.rs[0];
+        if (sliced) {
+            hipStream_t saved = c.stream;
+            HIPCHK(hipStreamWaitEvent(c.trsm_stream, c.ev_pc, 0));
+            c.stream = c.trsm_stream;
+            const int rc = solve_rest(r);
+            if (!rc) HIPCHK(hipEventRecord(c.ev_t5, c.stream));
+            c.stream = saved;
+            if (rc) return rc;
+        }
         HIPCHK(hipStreamWaitEvent(c.stream, c.ev_t5, 0));
         const int64_t s0 = lnext - loff;
-        if (s0 > 0)
-            launch_copy2d(r.A01, wA01, r.A01Rcv, Nl, c.nlayr, s0, c.stream);
-        if (wA01 - s0 - v > 0)
+        if (!direct && s0 > dead)
+            launch_copy2d(r.A01 + dead, wA01, r.A01Rcv + dead, Nl, c.nlayr,
+                          s0 - dead, c.stream);
+        if (!direct && wA01 - s0 - v > 0)
             launch_copy2d(r.A01 + s0 + v, wA01, r.A01Rcv + s0 + v, Nl,
                           c.nlayr, wA01 - s0 - v, c.stream);
     }
@@ -1552,11 +1736,15 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
     // pivot D2H), so anything enqueued after it cannot overlap the panel.
     for (auto &r : c.rs) {
         if (look && r.pj == ncol) {
-            if (gemm_piece(r, loff, lnext - loff, gcap)) return CONFLUX_LU_EHIP;
+            // (dead: with Py = 1 this first piece is the column block of
+            // the panel just factored, which no later step reads)
+            if (gemm_piece(r, loff + dead, lnext - loff - dead, gcap))
+                return CONFLUX_LU_EHIP;
             if (gemm_piece(r, lnext + v, Nl - (lnext + v), gcap))
                 return CONFLUX_LU_EHIP;
         } else {
-            if (gemm_piece(r, loff, wA01, gcap)) return CONFLUX_LU_EHIP;
+            if (gemm_piece(r, loff + dead, wA01 - dead, gcap))
+                return CONFLUX_LU_EHIP;
         }
     }
     // (c) lookahead: step k+1's panel chain on the panel stream, gated on
@@ -3500,6 +3688,69 @@ int conflux_lu_debug_trsm_ld(int side_right, int trans, int v, int64_t n,
     for (auto &e : c.evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     (void)hipStreamDestroy(c.stream);
     return rc;
+}
+
+// select the one-rank direct step for this process (bit mask, see
+// one_rank_direct_mode; 0 = the staged path); returns the previous mode.
+// Read at the start of each factorization.
+int conflux_lu_debug_set_one_rank_direct(int mode) {
+    const int prev = one_rank_direct_mode();
+    g_one_rank_direct = mode & ORD_ALL;
+    return prev;
+}
+
+// The stripe solves out of place, as the one-rank direct step uses them: the
+// window of Xs (host, leading dimension lds) at column soff is solved into
+// the window of Xd (host, ldd) at column doff; side_right -> windows are n x
+// v and the result is Xs_win * U^-1 (T upper), else v x n and L^-1 * Xs_win
+// (T unit lower).  Xd == NULL solves in place in Xs (ldd, doff ignored).
+// Both arrays are written back whole, so a caller sees that nothing outside
+// the destination window changed and that Xs was only read.
+int conflux_lu_debug_trsm_oop(int side_right, int v, int64_t n, int64_t lds,
+                              int64_t soff, int64_t ldd, int64_t doff,
+                              const double *T, double *Xs, double *Xd) {
+    const int64_t w = side_right ? i64(v) : n;
+    if (v <= 0 || n <= 0 || !T || !Xs || soff < 0 || lds < soff + w ||
+        (Xd && (doff < 0 || ldd < doff + w)) || n > INT32_MAX ||
+        !conflux_trsm_stripe_fits(v))
+        return CONFLUX_LU_EARG;
+    const int64_t rows = side_right ? n : i64(v);
+    double *dT = nullptr, *dS = nullptr, *dD = nullptr, *ws = nullptr;
+    auto cleanup = [&]() {
+        for (double *p : {dT, dS, dD, ws})
+            if (p) (void)hipFree(p);
+    };
+    hipError_t e = hipMalloc(&dT, i64(v) * v * 8);
+    if (e == hipSuccess) e = hipMalloc(&dS, rows * lds * 8);
+    if (e == hipSuccess && Xd) e = hipMalloc(&dD, rows * ldd * 8);
+    if (e == hipSuccess)
+        e = hipMalloc(&ws, conflux_trsm_stripe_ws_doubles(v) * 8);
+    if (e == hipSuccess)
+        e = hipMemcpy(dT, T, i64(v) * v * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMemcpy(dS, Xs, rows * lds * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess && Xd)
+        e = hipMemcpy(dD, Xd, rows * ldd * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        double *dst = Xd ? dD + doff : dS + soff;
+        const int64_t ld2 = Xd ? ldd : lds;
+        launch_trsm_pack_tri(dT, v, v, side_right ? 0 : 1, 0, ws, nullptr);
+        if (side_right)
+            launch_trsm_right_stripe_packed(ws, dS + soff, lds, dst, ld2, v, n,
+                                            nullptr);
+        else
+            launch_trsm_left_stripe_packed(ws, dS + soff, lds, dst, ld2, v, n,
+                                           nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess)
+        e = hipMemcpy(Xs, dS, rows * lds * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && Xd)
+        e = hipMemcpy(Xd, dD, rows * ldd * 8, hipMemcpyDeviceToHost);
+    cleanup();
+    HIPCHK(e);
+    return CONFLUX_LU_OK;
 }
 
 // X (v x N) <- T^-1 X with T (v x ldt host, only its triangle read)

@@ -2964,10 +2964,13 @@ __device__ inline int trs_blk(int pb, int jb) {
     return ((jb >> 5) * ((jb >> 5) + 1) / 2 + (pb >> 5)) * 1024;
 }
 
-// X (M x v, row-major) <- X * U^-1 or X * L^-T; U = the packed triangle.
+// Xd (M x v, row-major) <- Xs * U^-1 or Xs * L^-T; U = the packed triangle.
+// A block reads its stripe of Xs once and writes it to Xd once, so Xd may be
+// Xs itself (the in-place solve: neither pointer is __restrict__) or another
+// array with its own leading dimension; Xs is not written in that case.
 __global__ __launch_bounds__(256) void k_trsm_right_stripe(
-    const double *__restrict__ U, double *__restrict__ X, int64_t ldx, int v,
-    int64_t M) {
+    const double *__restrict__ U, const double *Xs, int64_t lds, double *Xd,
+    int64_t ldd, int v, int64_t M) {
     __shared__ double sX[TRS_MAXP][TRS_W][33];  // [panel][row][col]
     __shared__ double sU[2][32][33];
     const int tid = threadIdx.x;
@@ -2991,7 +2994,7 @@ __global__ __launch_bounds__(256) void k_trsm_right_stripe(
     load_u_regs(0, 0);
     for (int i = tid; i < TRS_W * v; i += 256) {
         const int r = i / v, cc = i - r * v;
-        sX[cc >> 5][r][cc & 31] = r < rows ? X[(r0 + r) * ldx + cc] : 0.0;
+        sX[cc >> 5][r][cc & 31] = r < rows ? Xs[(r0 + r) * lds + cc] : 0.0;
     }
     write_u(0);
     __syncthreads();
@@ -3041,14 +3044,15 @@ __global__ __launch_bounds__(256) void k_trsm_right_stripe(
     }
     for (int i = tid; i < rows * v; i += 256) {
         const int r = i / v, cc = i - r * v;
-        X[(r0 + r) * ldx + cc] = sX[cc >> 5][r][cc & 31];
+        Xd[(r0 + r) * ldd + cc] = sX[cc >> 5][r][cc & 31];
     }
 }
 
-// X (v x N, row-major) <- L^-1 * X, L unit lower = the packed triangle.
+// Xd (v x N, row-major) <- L^-1 * Xs, L unit lower = the packed triangle;
+// Xd == Xs is the in-place solve, as above.
 __global__ __launch_bounds__(256) void k_trsm_left_stripe(
-    const double *__restrict__ L, double *__restrict__ X, int64_t ldx, int v,
-    int64_t N) {
+    const double *__restrict__ L, const double *Xs, int64_t lds, double *Xd,
+    int64_t ldd, int v, int64_t N) {
     __shared__ double sX[TRS_MAXP][32][TRS_W + 1];  // [panel][k][col]
     __shared__ double sL[2][32][33];
     const int tid = threadIdx.x;
@@ -3073,7 +3077,7 @@ __global__ __launch_bounds__(256) void k_trsm_left_stripe(
     for (int i = tid; i < v * TRS_W; i += 256) {
         const int r = i >> 5, cc = i & (TRS_W - 1);
         sX[r >> 5][r & 31][cc] =
-            cc < cols ? X[(int64_t)r * ldx + c0 + cc] : 0.0;
+            cc < cols ? Xs[(int64_t)r * lds + c0 + cc] : 0.0;
     }
     write_l(0);
     __syncthreads();
@@ -3120,7 +3124,7 @@ __global__ __launch_bounds__(256) void k_trsm_left_stripe(
     }
     for (int i = tid; i < v * TRS_W; i += 256) {
         const int r = i >> 5, cc = i & (TRS_W - 1);
-        if (cc < cols) X[(int64_t)r * ldx + c0 + cc] = sX[r >> 5][r & 31][cc];
+        if (cc < cols) Xd[(int64_t)r * ldd + c0 + cc] = sX[r >> 5][r & 31][cc];
     }
 }
 
@@ -3134,26 +3138,44 @@ int64_t conflux_trsm_stripe_ws_doubles(int v) {
     return np * (np + 1) / 2 * 1024;
 }
 
+void launch_trsm_pack_tri(const double *T, int64_t ldt, int v, int swap,
+                          int tr, double *ws, hipStream_t s) {
+    if (v <= 0) return;
+    const int nblk = (int)(conflux_trsm_stripe_ws_doubles(v) / 1024);
+    hipLaunchKernelGGL(k_trsm_pack_tri, dim3(nblk), dim3(256), 0, s, T, ldt, ws,
+                       swap, tr);
+}
+
+void launch_trsm_right_stripe_packed(const double *ws, const double *Xs,
+                                     int64_t lds, double *Xd, int64_t ldd,
+                                     int v, int64_t M, hipStream_t s) {
+    if (M <= 0 || v <= 0) return;
+    hipLaunchKernelGGL(k_trsm_right_stripe, dim3(cdiv64(M, TRS_W)), dim3(256),
+                       0, s, ws, Xs, lds, Xd, ldd, v, M);
+}
+
+void launch_trsm_left_stripe_packed(const double *ws, const double *Xs,
+                                    int64_t lds, double *Xd, int64_t ldd,
+                                    int v, int64_t N, hipStream_t s) {
+    if (N <= 0 || v <= 0) return;
+    hipLaunchKernelGGL(k_trsm_left_stripe, dim3(cdiv64(N, TRS_W)), dim3(256),
+                       0, s, ws, Xs, lds, Xd, ldd, v, N);
+}
+
 void launch_trsm_right_stripe(const double *U, int64_t ldu, double *X,
                               int64_t ldx, int v, int64_t M, int trans,
                               double *ws, hipStream_t s) {
     if (M <= 0 || v <= 0) return;
-    const int nblk = (int)(conflux_trsm_stripe_ws_doubles(v) / 1024);
-    hipLaunchKernelGGL(k_trsm_pack_tri, dim3(nblk), dim3(256), 0, s, U, ldu, ws,
-                       trans ? 1 : 0, trans ? 1 : 0);
-    hipLaunchKernelGGL(k_trsm_right_stripe, dim3(cdiv64(M, TRS_W)), dim3(256),
-                       0, s, ws, X, ldx, v, M);
+    launch_trsm_pack_tri(U, ldu, v, trans ? 1 : 0, trans ? 1 : 0, ws, s);
+    launch_trsm_right_stripe_packed(ws, X, ldx, X, ldx, v, M, s);
 }
 
 void launch_trsm_left_stripe(const double *L, int64_t ldl, double *X,
                              int64_t ldx, int v, int64_t N, double *ws,
                              hipStream_t s) {
     if (N <= 0 || v <= 0) return;
-    const int nblk = (int)(conflux_trsm_stripe_ws_doubles(v) / 1024);
-    hipLaunchKernelGGL(k_trsm_pack_tri, dim3(nblk), dim3(256), 0, s, L, ldl, ws,
-                       1, 0);
-    hipLaunchKernelGGL(k_trsm_left_stripe, dim3(cdiv64(N, TRS_W)), dim3(256),
-                       0, s, ws, X, ldx, v, N);
+    launch_trsm_pack_tri(L, ldl, v, 1, 0, ws, s);
+    launch_trsm_left_stripe_packed(ws, X, ldx, X, ldx, v, N, s);
 }
 
 void launch_trsm_right_mfma(const double *U, int64_t ldu, double *X,

@@ -84,6 +84,20 @@ void launch_trsm_right_stripe(const double *U, int64_t ldu, double *X,
 void launch_trsm_left_stripe(const double *L, int64_t ldl, double *X,
                              int64_t ldx, int v, int64_t N, double *ws,
                              hipStream_t s);
+// The same solves in two parts, for callers that use one triangle for several
+// launches or solve out of place.  launch_trsm_pack_tri fills ws from the
+// triangle ((swap, tr) = (0, 0): X U^-1, (1, 1): X L^-T, (1, 0): L^-1 X); the
+// *_packed launches read Xs (leading dimension lds) and write Xd (ldd).  Xd
+// may be Xs (in place, what the two launches above do); otherwise the two
+// windows must not overlap and Xs is left untouched.
+void launch_trsm_pack_tri(const double *T, int64_t ldt, int v, int swap,
+                          int tr, double *ws, hipStream_t s);
+void launch_trsm_right_stripe_packed(const double *ws, const double *Xs,
+                                     int64_t lds, double *Xd, int64_t ldd,
+                                     int v, int64_t M, hipStream_t s);
+void launch_trsm_left_stripe_packed(const double *ws, const double *Xs,
+                                    int64_t lds, double *Xd, int64_t ldd,
+                                    int v, int64_t N, hipStream_t s);
 // solve_kernels.hip: X (v x N) <- T^-1 X, T lower/upper, unit/non-unit, any
 // v >= 1, read in place (ldt = the global N); C (M x nrhs) -= A B, nrhs <= 16
 void launch_trsm_left_tri_mfma(const double *T, int64_t ldt, double *X,

@@ -34,13 +34,17 @@ def main(path, nt=32):
                          short(r["Kernel_Name"]), int(r["Grid_Size_X"]),
                          int(r["Workgroup_Size_X"])))
     rows.sort()
-    panel = ("k_panel_factor", "k_panel_glue_prep", "k_panel_glue_update")
-    # chains: split the panel-kernel sequence where a non-panel kernel on the
-    # critical path (a TRSM) lies between two panel kernels
+    # the leaf is k_panel_factor or, since r06, k_panel_factor_reg
+    leaf = ("k_panel_factor", "k_panel_factor_reg")
+    panel = leaf + ("k_panel_glue_prep", "k_panel_glue_update")
+    # chains: split the panel-kernel sequence where the right solve (main
+    # stream, always inside the stretch) lies between two panel kernels; the
+    # left solve does not qualify: with the one-rank direct step its rest
+    # runs next to the first leaves of the next chain
     chains, cur = [], []
     last_trsm = -1
     for i, (s, e, n, g, w) in enumerate(rows):
-        if n.startswith("k_trsm"):
+        if n.startswith("k_trsm_right"):
             last_trsm = i
         if n in panel:
             if cur and last_trsm > cur[-1]:
@@ -55,7 +59,7 @@ def main(path, nt=32):
         if step == nt - 1:
             continue  # next chain belongs to the next factorization
         t0 = max(rows[i][1] for i in chains[ci])
-        nxt = [i for i in chains[ci + 1] if rows[i][2] == "k_panel_factor"]
+        nxt = [i for i in chains[ci + 1] if rows[i][2] in leaf]
         t1 = rows[nxt[0]][0]
         fam = defaultdict(float)
         segs = []
