@@ -117,6 +117,21 @@ def _load():
         lib.conflux_lu_debug_trsm_left.argtypes
     lib.conflux_lu_debug_update_skinny_t.argtypes = \
         lib.conflux_lu_debug_update_skinny.argtypes
+    # kernel pins (whole host buffers up and down; EARG before any launch)
+    i32, i64, ptr = ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p
+    lib.conflux_lu_debug_dgemm_ex.argtypes = [
+        i32, i32, i32, i64, i32, i64, i64, i64, i64, ptr, ptr, ptr]
+    lib.conflux_lu_debug_set_gemm_strip.argtypes = [i32]
+    lib.conflux_lu_debug_set_gemm_ntc.argtypes = [i32]
+    lib.conflux_lu_debug_dgemm_nt.argtypes = [
+        i32, i64, i32, i64, i64, i64, i64, ptr, ptr, ptr,
+        i32, i32, i64, i32, i32, i32, i32]
+    lib.conflux_lu_debug_potrf32.argtypes = [i32, i64, i64, ptr]
+    lib.conflux_lu_debug_getrf32_nopiv.argtypes = [i32, i64, i64, ptr]
+    lib.conflux_lu_debug_trsm32.argtypes = [i32, i32, i64, i64, i64, ptr, ptr]
+    lib.conflux_lu_debug_potrf_tile.argtypes = [i32, i64, i64, ptr]
+    lib.conflux_lu_debug_poke_factor.argtypes = [ptr, i64, i64,
+                                                 ctypes.c_double]
     return lib
 
 

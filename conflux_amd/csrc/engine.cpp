@@ -2666,7 +2666,7 @@ static int validate_common(conflux_lu_ctx *c, bool chol, double *resid) {
         VCHK(hipMalloc(&d_pm, N * 4));
     }
     VCHK(hipMalloc(&C, i64(v) * N * 8));
-    VCHK(hipMalloc(&d_acc, 2 * 8));
+    VCHK(hipMalloc(&d_acc, (2 + CONFLUX_FROB2_WS_DOUBLES) * 8));
     VCHK(hipMemsetAsync(d_acc, 0, 16, c->stream));
 
     // assemble global A (input snapshot) and F from the tile-cyclic locals
@@ -2725,7 +2725,7 @@ static int validate_common(conflux_lu_ctx *c, bool chol, double *resid) {
     if (!chol) {
         VCHK(hipMemcpyAsync(d_pm, c->pivotInds.data(), N * 4,
                             hipMemcpyHostToDevice, c->stream));
-        launch_frob2(Ag, N * N, d_acc + 1, c->stream);
+        launch_frob2(Ag, N * N, d_acc + 1, d_acc + 2, c->stream);
         for (int64_t i0 = 0; i0 < N; i0 += v) {
             const int K = (int)(i0 + v);
             // PA stripe: rows perm[i0 .. i0+v)
@@ -2735,13 +2735,13 @@ static int validate_common(conflux_lu_ctx *c, bool chol, double *resid) {
             launch_tril_unit_rows(Fg + i0 * N, N, L, N, v, i0, K, c->stream);
             launch_triu_rows(Fg + i0 * N, N, v, i0, c->stream);
             launch_dgemm_f64(L, N, Fg, N, C, N, v, N, K, c->stream);
-            launch_frob2(C, i64(v) * N, d_acc, c->stream);
+            launch_frob2(C, i64(v) * N, d_acc, d_acc + 2, c->stream);
         }
     } else {
         // symmetrize from the lower triangle (the generator / reference
         // CholeskyIO fill lower-stored input, dsyrk 'L')
         launch_transpose_add_lower(Ag, N, c->stream);
-        launch_frob2(Ag, N * N, d_acc + 1, c->stream);
+        launch_frob2(Ag, N * N, d_acc + 1, d_acc + 2, c->stream);
         // Fg <- tril(Fg) in place (upper half of the stored L is junk);
         // the stripe GEMMs then read L directly out of Fg
         launch_tril(Fg, Fg, N, c->stream);
@@ -2750,7 +2750,7 @@ static int validate_common(conflux_lu_ctx *c, bool chol, double *resid) {
             launch_copy2d(Ag + i0 * N, N, C, N, v, N, c->stream);
             launch_dgemm_f64_nt(Fg + i0 * N, N, Fg, N, C, N, v, N, K,
                                 c->stream);
-            launch_frob2(C, i64(v) * N, d_acc, c->stream);
+            launch_frob2(C, i64(v) * N, d_acc, d_acc + 2, c->stream);
         }
     }
     double acc[2] = {0, 0};
@@ -3455,6 +3455,212 @@ int conflux_lu_debug_dgemm(int M, int64_t N, int K, const double *A,
     HIPCHK(hipMemcpy(C, dC, i64(M) * N * 8, hipMemcpyDeviceToHost));
     (void)hipFree(dA); (void)hipFree(dB); (void)hipFree(dC);
     (void)hipStreamDestroy(s);
+    return CONFLUX_LU_OK;
+}
+
+// ---- kernel pins: one launcher per entry, on host buffers that are uploaded
+// and downloaded WHOLE (padding rows and columns included), so a test sees
+// every byte a kernel could have touched.  Each returns CONFLUX_LU_EARG before
+// any launch for a size, leading dimension or mask argument outside the
+// launcher's domain.
+}  // extern "C"
+namespace {
+struct PinBuf {  // device image of one whole host buffer
+    double *d = nullptr;
+    int64_t n = 0;
+    ~PinBuf() {
+        if (d) (void)hipFree(d);
+    }
+    int up(const double *h, int64_t nelem) {
+        n = nelem;
+        HIPCHK(hipMalloc(&d, n * 8));
+        HIPCHK(hipMemcpy(d, h, n * 8, hipMemcpyHostToDevice));
+        return 0;
+    }
+    int down(double *h) const {
+        HIPCHK(hipMemcpy(h, d, n * 8, hipMemcpyDeviceToHost));
+        return 0;
+    }
+};
+struct PinStream {
+    hipStream_t s{};
+    bool live = false;
+    ~PinStream() {
+        if (live) (void)hipStreamDestroy(s);
+    }
+    int make() {
+        HIPCHK(hipStreamCreate(&s));
+        live = true;
+        return 0;
+    }
+};
+const int64_t PIN_MAX_ELEMS = int64_t(1) << 28;  // 2 GiB per buffer
+bool pin_dims_ok(int64_t rows, int64_t ld, int64_t width) {
+    return rows > 0 && width > 0 && ld >= width && ld <= PIN_MAX_ELEMS &&
+           rows <= PIN_MAX_ELEMS / ld;
+}
+}  // namespace
+extern "C" {
+
+// launch_dgemm_f64 on the top-left M x N of a c_rows x ldc host C (A: M x
+// lda, B: K x ldb) with `variant` selected for this one call and `maxwg` as
+// the launcher takes it.
+int conflux_lu_debug_dgemm_ex(int variant, int maxwg, int M, int64_t N, int K,
+                              int64_t lda, int64_t ldb, int64_t ldc,
+                              int64_t c_rows, const double *A, const double *B,
+                              double *C) {
+    if (variant < 0 || variant > 3 || maxwg < 0 || !A || !B || !C ||
+        c_rows < M || !pin_dims_ok(M, lda, K) || !pin_dims_ok(K, ldb, N) ||
+        !pin_dims_ok(c_rows, ldc, N))
+        return CONFLUX_LU_EARG;
+    PinStream st;
+    PinBuf dA, dB, dC;
+    if (st.make() || dA.up(A, M * lda) || dB.up(B, K * ldb) ||
+        dC.up(C, c_rows * ldc))
+        return CONFLUX_LU_EHIP;
+    const int prev = g_dgemm_variant;
+    g_dgemm_variant = variant;
+    launch_dgemm_f64(dA.d, lda, dB.d, ldb, dC.d, ldc, M, N, K, st.s, maxwg);
+    g_dgemm_variant = prev;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st.s));
+    return dC.down(C);
+}
+
+// strip width of the GEMM tile order (0/1 = flat) and the non-temporal C
+// epilogue of the w8 kernel, for this process; each returns the previous value
+int conflux_lu_debug_set_gemm_strip(int w) {
+    return conflux_gemm_set_strip_w(w);
+}
+int conflux_lu_debug_set_gemm_ntc(int on) { return conflux_gemm_set_ntc(on); }
+
+// C (top-left M x N of c_rows x ldc) -= A (M x lda) B^T (B: N x ldb).  v == 0:
+// launch_dgemm_f64_nt; otherwise launch_dgemm_f64_nt_tril with that mask.
+// A == B (one host pointer, as in potrf_tile) is uploaded once and passed
+// twice; it then needs lda == ldb.
+int conflux_lu_debug_dgemm_nt(int M, int64_t N, int K, int64_t lda,
+                              int64_t ldb, int64_t ldc, int64_t c_rows,
+                              const double *A, const double *B, double *C,
+                              int v, int r0off, int64_t c0off, int Px, int Py,
+                              int pi, int pj) {
+    if (!A || !B || !C || c_rows < M || !pin_dims_ok(M, lda, K) ||
+        !pin_dims_ok(N, ldb, K) || !pin_dims_ok(c_rows, ldc, N) ||
+        (A == B && lda != ldb) || v < 0)
+        return CONFLUX_LU_EARG;
+    if (v > 0 &&
+        (v % 128 != 0 || M % v != 0 || N % v != 0 || r0off < 0 || c0off < 0 ||
+         r0off % v != 0 || c0off % v != 0 || r0off > (1 << 28) ||
+         c0off > (1 << 28) || Px < 1 || Py < 1 || Px > 4096 || Py > 4096 ||
+         pi < 0 || pi >= Px || pj < 0 || pj >= Py))
+        return CONFLUX_LU_EARG;
+    const bool alias = A == B;
+    PinStream st;
+    PinBuf dA, dB, dC;
+    if (st.make() || dC.up(C, c_rows * ldc)) return CONFLUX_LU_EHIP;
+    if (alias) {
+        if (dA.up(A, std::max<int64_t>(M, N) * lda)) return CONFLUX_LU_EHIP;
+    } else if (dA.up(A, M * lda) || dB.up(B, N * ldb)) {
+        return CONFLUX_LU_EHIP;
+    }
+    const double *pB = alias ? dA.d : dB.d;
+    if (v == 0)
+        launch_dgemm_f64_nt(dA.d, lda, pB, ldb, dC.d, ldc, M, N, K, st.s);
+    else
+        launch_dgemm_f64_nt_tril(dA.d, lda, pB, ldb, dC.d, ldc, M, N, K, v,
+                                 r0off, c0off, Px, Py, pi, pj, st.s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st.s));
+    return dC.down(C);
+}
+
+// launch_potrf32 / launch_getrf32_nopiv on the top-left nb x nb of a rows x
+// lda host A
+static int debug_factor32(bool chol, int nb, int64_t lda, int64_t rows,
+                          double *A) {
+    if (!A || nb < 1 || nb > 32 || rows < nb || !pin_dims_ok(rows, lda, nb))
+        return CONFLUX_LU_EARG;
+    PinStream st;
+    PinBuf dA;
+    if (st.make() || dA.up(A, rows * lda)) return CONFLUX_LU_EHIP;
+    if (chol)
+        launch_potrf32(dA.d, lda, nb, st.s);
+    else
+        launch_getrf32_nopiv(dA.d, lda, nb, st.s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st.s));
+    return dA.down(A);
+}
+int conflux_lu_debug_potrf32(int nb, int64_t lda, int64_t rows, double *A) {
+    return debug_factor32(true, nb, lda, rows, A);
+}
+int conflux_lu_debug_getrf32_nopiv(int nb, int64_t lda, int64_t rows,
+                                   double *A) {
+    return debug_factor32(false, nb, lda, rows, A);
+}
+
+// launch_trsm_right_upper32: X (M x ldx, first nb columns) <- X U^-1 (trans =
+// 0, U upper) or X L^-T (trans = 1, L lower), U / L the top-left nb x nb of an
+// nb x ldu host array
+int conflux_lu_debug_trsm32(int trans, int nb, int64_t M, int64_t ldu,
+                            int64_t ldx, const double *U, double *X) {
+    if (!U || !X || (trans != 0 && trans != 1) || nb < 1 || nb > 32 ||
+        !pin_dims_ok(nb, ldu, nb) || !pin_dims_ok(M, ldx, nb))
+        return CONFLUX_LU_EARG;
+    PinStream st;
+    PinBuf dU, dX;
+    if (st.make() || dU.up(U, nb * ldu) || dX.up(X, M * ldx))
+        return CONFLUX_LU_EHIP;
+    launch_trsm_right_upper32(dU.d, ldu, dX.d, ldx, nb, M, trans, st.s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st.s));
+    return dX.down(X);
+}
+
+// the engine's blocked potrf_tile (potrf32 / trsm32 / NT GEMM chain) on the
+// top-left v x v of a rows x ld host T
+int conflux_lu_debug_potrf_tile(int v, int64_t ld, int64_t rows, double *T) {
+    if (!T || v < 1 || v > 4096 || rows < v || !pin_dims_ok(rows, ld, v))
+        return CONFLUX_LU_EARG;
+    Ctx c;
+    c.v = v;
+    PinStream st;
+    PinBuf dT;
+    if (st.make() || dT.up(T, rows * ld)) return CONFLUX_LU_EHIP;
+    c.stream = st.s;
+    int rc = potrf_tile(c, dT.d, ld);
+    if (!rc && hipGetLastError() != hipSuccess) rc = CONFLUX_LU_EHIP;
+    if (hipStreamSynchronize(st.s) != hipSuccess) rc = CONFLUX_LU_EHIP;
+    for (auto &e : c.evs) {
+        (void)hipEventDestroy(e.a);
+        (void)hipEventDestroy(e.b);
+    }
+    return rc ? rc : dT.down(T);
+}
+
+// Fres[grow][gcol] += delta on the pk == 0 rank that owns the element (rows in
+// pivoted order, columns global; validate_common's owner map).  Simulation
+// grids and the one-rank real mode; EARG without stored factors or when
+// world > 1.
+int conflux_lu_debug_poke_factor(conflux_lu_ctx *c, int64_t grow, int64_t gcol,
+                                 double delta) {
+    if (!c || !c->store_factors || c->factored_kind == 0 ||
+        (!c->sim && c->world > 1) || grow < 0 || gcol < 0 || grow >= c->M ||
+        gcol >= c->N)
+        return CONFLUX_LU_EARG;
+    const int v = c->v;
+    const int ti = (int)(grow / v), tj = (int)(gcol / v);
+    RankState *r = c->sim ? get_rs(*c, ti % c->Px, tj % c->Py, 0) : &c->rs[0];
+    const int64_t lrow = i64(ti / c->Px) * v + grow % v;
+    const int64_t lcol = i64(tj / c->Py) * v + gcol % v;
+    if (!r || !r->Fres || lrow >= c->Ml || lcol >= c->Nl ||
+        (!c->sim && (c->Px != 1 || c->Py != 1)))
+        return CONFLUX_LU_EARG;
+    double *p = r->Fres + lrow * c->Nl + lcol;
+    double x = 0;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(&x, p, 8, hipMemcpyDeviceToHost));
+    x += delta;
+    HIPCHK(hipMemcpy(p, &x, 8, hipMemcpyHostToDevice));
     return CONFLUX_LU_OK;
 }
 

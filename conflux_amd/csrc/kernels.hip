@@ -23,6 +23,7 @@
 // All fp64.  No CUDA-compat shims, no library GEMMs on the hot path.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 
@@ -2116,6 +2117,11 @@ __global__ __launch_bounds__(512, 4) void k_dgemm_f64_w8_nt(
 // the lane-linear LDS image reads conflict-free (guide rule 21 / T2).
 // Layouts: As [BK][BM] row-of-m linear, A-chunk (row, p) stored at p^(row&7);
 //          Bs [BK][BN] linear, B-chunk (k, np) stored at np^((k&3)<<1).
+// Envelope (checked by launch_dgemm_f64, which runs k_dgemm_f64_w8 instead
+// when any of it fails): K % 16 == 0 (no K tail: a short last K-tile would
+// read rows of B that do not exist), lda, ldb and N even and A, B 16-byte
+// aligned (every 16-byte piece is then aligned and lies wholly inside or
+// wholly outside the matrix).
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(512, 4) void k_dgemm_f64_glds(
     const double *__restrict__ A, int64_t lda, const double *__restrict__ B,
@@ -3225,8 +3231,12 @@ __global__ void k_triu(const double *__restrict__ F, double *__restrict__ U,
     }
 }
 
-__global__ void k_frob2(const double *__restrict__ A, int64_t n,
-                        double *__restrict__ out) {
+// *out += sum A[i]^2 in two launches with a FIXED summation order: each block
+// leaves its partial in ws[blockIdx.x], then one block adds the partials in
+// index order.  (Blocks adding to *out atomically combine in arrival order,
+// which made the validators' value differ in its last bits from run to run.)
+__global__ void k_frob2_part(const double *__restrict__ A, int64_t n,
+                             double *__restrict__ ws) {
     __shared__ double part[256];
     const int tid = threadIdx.x;
     double s = 0;
@@ -3239,7 +3249,22 @@ __global__ void k_frob2(const double *__restrict__ A, int64_t n,
         if (tid < w) part[tid] += part[tid + w];
         __syncthreads();
     }
-    if (tid == 0) (void)atomicAdd(out, part[0]);
+    if (tid == 0) ws[blockIdx.x] = part[0];
+}
+
+__global__ __launch_bounds__(256) void k_frob2_sum(
+    const double *__restrict__ ws, int nparts, double *__restrict__ out) {
+    __shared__ double part[256];
+    const int tid = threadIdx.x;
+    double s = 0;
+    for (int i = tid; i < nparts; i += 256) s += ws[i];
+    part[tid] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) part[tid] += part[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) *out += part[0];
 }
 
 void launch_tril_unit(const double *F, double *L, int64_t n, hipStream_t s) {
@@ -3313,11 +3338,14 @@ void launch_triu(const double *F, double *U, int64_t n, hipStream_t s) {
     hipLaunchKernelGGL(k_triu, dim3(cap_grid(n * n)), dim3(256), 0, s, F,
                        U, n);
 }
-void launch_frob2(const double *A, int64_t nelem, double *out, hipStream_t s) {
+void launch_frob2(const double *A, int64_t nelem, double *out, double *ws,
+                  hipStream_t s) {
     int blocks = (int)cdiv64(nelem, 256 * 16);
-    if (blocks > 4096) blocks = 4096;
+    if (blocks > CONFLUX_FROB2_WS_DOUBLES) blocks = CONFLUX_FROB2_WS_DOUBLES;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(k_frob2, dim3(blocks), dim3(256), 0, s, A, nelem, out);
+    hipLaunchKernelGGL(k_frob2_part, dim3(blocks), dim3(256), 0, s, A, nelem,
+                       ws);
+    hipLaunchKernelGGL(k_frob2_sum, dim3(1), dim3(256), 0, s, ws, blocks, out);
 }
 
 void launch_potrf32(double *A, int64_t lda, int nb, hipStream_t s) {
@@ -3332,22 +3360,45 @@ void launch_getrf32_nopiv(double *A, int64_t lda, int nb, hipStream_t s) {
 
 int g_dgemm_variant = -1;  // 0 = 4-wave, 1 = 8-wave; env CONFLUX_GEMM_VARIANT
 
+// process-global like g_dgemm_variant: the environment gives the default on
+// first use, the setters below override it and return the previous value
+static int g_gemm_strip_w = -1;
+static int g_gemm_ntc = -1;
+
 static int gemm_strip_w() {  // strip width in tiles; 0/1 = flat order
-    static int w = -1;
-    if (w < 0) {
+    if (g_gemm_strip_w < 0) {
         const char *e = getenv("CONFLUX_GEMM_STRIP");
-        w = e ? atoi(e) : 8;
+        g_gemm_strip_w = e ? std::max(0, atoi(e)) : 8;
     }
-    return w;
+    return g_gemm_strip_w;
 }
 
 static int gemm_ntc() {  // non-temporal C epilogue (w8 kernel)
-    static int v = -1;
-    if (v < 0) {
+    if (g_gemm_ntc < 0) {
         const char *e = getenv("CONFLUX_GEMM_NTC");
-        v = e ? atoi(e) : 0;
+        g_gemm_ntc = e ? (atoi(e) != 0) : 0;
     }
-    return v;
+    return g_gemm_ntc;
+}
+
+int conflux_gemm_set_strip_w(int w) {
+    const int prev = gemm_strip_w();
+    g_gemm_strip_w = std::max(0, w);
+    return prev;
+}
+
+int conflux_gemm_set_ntc(int on) {
+    const int prev = gemm_ntc();
+    g_gemm_ntc = on != 0;
+    return prev;
+}
+
+// k_dgemm_f64_glds stages whole 16-byte pieces and has no K tail: it may run
+// only inside this envelope.  Outside it variant 2 launches the w8 kernel.
+static bool gemm_glds_ok(const double *A, int64_t lda, const double *B,
+                         int64_t ldb, int64_t N, int K) {
+    return K % GEMM_BK == 0 && lda % 2 == 0 && ldb % 2 == 0 && N % 2 == 0 &&
+           (uintptr_t)A % 16 == 0 && (uintptr_t)B % 16 == 0;
 }
 
 void launch_dgemm_f64(const double *A, int64_t lda, const double *B,
@@ -3361,19 +3412,21 @@ void launch_dgemm_f64(const double *A, int64_t lda, const double *B,
     const int ntm = (int)cdiv64(M, GEMM_BM);
     const int ntn = (int)cdiv64(N, GEMM_BN);
     const int sw = gemm_strip_w();
+    int variant = g_dgemm_variant;
+    if (variant == 2 && !gemm_glds_ok(A, lda, B, ldb, N, K)) variant = 1;
     int nwg = ntm * ntn;
     // cap (persistent w8 kernel only): leave CUs free for a concurrent panel
-    if (maxwg > 0 && g_dgemm_variant == 1 && nwg > maxwg) nwg = maxwg;
-    if (g_dgemm_variant == 3) {
+    if (maxwg > 0 && variant == 1 && nwg > maxwg) nwg = maxwg;
+    if (variant == 3) {
         const int ntm2 = (int)cdiv64(M, 256);
         hipLaunchKernelGGL(k_dgemm_f64_bm256, dim3(ntm2 * ntn), dim3(512), 0,
                            s, A, lda, B, ldb, C, ldc, M, N, K, ntm2, ntn, sw);
         return;
     }
-    if (g_dgemm_variant == 2)
+    if (variant == 2)
         hipLaunchKernelGGL(k_dgemm_f64_glds, dim3(ntm * ntn), dim3(512), 0, s,
                            A, lda, B, ldb, C, ldc, M, N, K, ntm, ntn, sw);
-    else if (g_dgemm_variant == 1)
+    else if (variant == 1)
         hipLaunchKernelGGL(k_dgemm_f64_w8, dim3(nwg), dim3(512), 0, s,
                            A, lda, B, ldb, C, ldc, M, N, K, ntm, ntn, sw,
                            gemm_ntc());

@@ -141,7 +141,11 @@ void launch_triu_rows(double *F, int64_t ldf, int rows, int64_t row0,
 void launch_transpose_add_lower(double *A, int64_t n, hipStream_t s);
 void launch_tril(const double *F, double *L, int64_t n, hipStream_t s);
 void launch_triu(const double *F, double *U, int64_t n, hipStream_t s);
-void launch_frob2(const double *A, int64_t nelem, double *out, hipStream_t s);
+// *out += sum A[i]^2, the same bits on every run; ws: CONFLUX_FROB2_WS_DOUBLES
+// doubles of device scratch (launches on one stream may share it)
+#define CONFLUX_FROB2_WS_DOUBLES 4096
+void launch_frob2(const double *A, int64_t nelem, double *out, double *ws,
+                  hipStream_t s);
 void launch_potrf32(double *A, int64_t lda, int nb, hipStream_t s);
 void launch_getrf32_nopiv(double *A, int64_t lda, int nb, hipStream_t s);
 void launch_dgemm_f64_nt(const double *A, int64_t lda, const double *B,
@@ -159,6 +163,12 @@ void launch_dgemm_f64(const double *A, int64_t lda, const double *B,
                       int64_t ldb, double *C, int64_t ldc, int M, int64_t N,
                       int K, hipStream_t s,
                       int maxwg = 0);
+// GEMM launch switches (CONFLUX_GEMM_VARIANT / _STRIP / _NTC give the
+// defaults; g_dgemm_variant < 0 = not read yet); the setters return the
+// previous value.
+extern int g_dgemm_variant;
+int conflux_gemm_set_strip_w(int w);
+int conflux_gemm_set_ntc(int on);
 void launch_pack_candidate(const double *A10, int64_t lda, const int *gri,
                            int f, int n_src, int n_out, int v, const int *idx,
                            double *cand, hipStream_t s);
