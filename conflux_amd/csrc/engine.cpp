@@ -3518,17 +3518,16 @@ int conflux_lu_debug_dgemm_ex(int variant, int maxwg, int M, int64_t N, int K,
     if (st.make() || dA.up(A, M * lda) || dB.up(B, K * ldb) ||
         dC.up(C, c_rows * ldc))
         return CONFLUX_LU_EHIP;
-    const int prev = g_dgemm_variant;
-    g_dgemm_variant = variant;
+    const int prev = conflux_gemm_set_variant(variant);
     launch_dgemm_f64(dA.d, lda, dB.d, ldb, dC.d, ldc, M, N, K, st.s, maxwg);
-    g_dgemm_variant = prev;
+    conflux_gemm_set_variant(prev);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st.s));
     return dC.down(C);
 }
 
 // strip width of the GEMM tile order (0/1 = flat) and the non-temporal C
-// epilogue of the w8 kernel, for this process; each returns the previous value
+// epilogue of the GemmW8 edition, for this process; each returns the previous value
 int conflux_lu_debug_set_gemm_strip(int w) {
     return conflux_gemm_set_strip_w(w);
 }

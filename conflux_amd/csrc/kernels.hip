@@ -1,7 +1,7 @@
 // kernels.hip — CDNA4 (gfx950) kernels of the MI355X-native CONFLUX LU engine.
 //
 // Re-expressions of the reference's compute units (SURVEY.md §2 checklist):
-//   k_dgemm_f64        <- trailing-update cblas_dgemm (conflux_opt.hpp:1628-1633)
+//   k_dgemm_mfma       <- trailing-update cblas_dgemm (conflux_opt.hpp:1628-1633)
 //                         and the panel-update GEMMs of blocked getrf/TRSM;
 //                         hand-written v_mfma_f64_16x16x4_f64, LDS-staged.
 //   k_panel_factor     <- LAPACKE_dgetrf partial pivoting
@@ -11,7 +11,7 @@
 //                         release/acquire slab handshake.
 //   k_trsm_*           <- cblas_dtrsm Right/Upper/NonUnit (:1347) and
 //                         Left/Lower/Unit (:1539), 32-wide diagonal blocks +
-//                         k_dgemm_f64 updates.
+//                         k_dgemm_mfma updates.
 //   k_row_gather/scatter/move, k_swap_map/k_rowperm_*, k_copy2d, ...
 //                      <- push_pivots_up / permute_rows / dlaswp / mcopy
 //                         (conflux_opt.hpp:176-218, utils.hpp:48-160,
@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
+#include <type_traits>
 
 #include "kernels.hpp"
 
@@ -1332,14 +1333,16 @@ __global__ __launch_bounds__(256) void k_trsm_right_upper32(
 // ---------------------------------------------------------------------------
 // MFMA fp64 GEMM:  C (M x N, ldc) -= A (M x K, lda) * B (K x N, ldb)
 // ---------------------------------------------------------------------------
-// 128x128 block tile, BK=16, 4 waves (2x2), 64x64 per wave as 4x4 fragments
-// of v_mfma_f64_16x16x4_f64.  Register-staged global->LDS with the
-// write-after-barrier placement (guide §5.5 T14); A transposed in LDS so
-// fragment reads are conflict-free; XCD-aware block swizzle (T1).
+// One kernel template, k_dgemm_mfma<Cfg>, instantiated once per edition (the
+// Gemm* configs below), and the async-staged k_dgemm_f64_glds further down.
+// Common to all: a BM x 128 block tile walked in K-tiles of BK; fragments of
+// v_mfma_f64_16x16x4_f64; XCD-aware block swizzle (T1) and the strip tile
+// order.  In the template A is transposed in LDS so fragment reads are
+// conflict-free.  GEMM_BM / GEMM_BK are the tile of every edition but
+// GemmBm256.
 #define GEMM_BM 128
 #define GEMM_BN 128
 #define GEMM_BK 16
-#define GEMM_TPB 256
 
 // tile order: strips of `strip_w` tile-columns walked row-major, so the
 // ~512 concurrently-resident workgroups form a 2D window (e.g. 64 wg =
@@ -1369,151 +1372,98 @@ DEVFN void gemm_tile_of(int wg, int ntm, int ntn, int strip_w, int &tm,
     }
 }
 
-__global__ __launch_bounds__(GEMM_TPB) void k_dgemm_f64(
+// Tile-cyclic lower-triangle mask of the NT edition (the Cholesky c4
+// single-launch update): workgroups whose GLOBAL v-tile row < v-tile col exit
+// immediately, so one rectangular launch covers the trapezoid of tiles with
+// i >= j and spends nothing on the rest.  mask.v == 0 disables.  A 128-wide
+// workgroup never straddles a v-tile boundary (v % 128 == 0 enforced by the
+// launcher).
+struct TriMask {
+    int v;          // global tile size (0 = no mask)
+    int r0off;      // launch-local row 0's offset within the rank-local A11
+    int64_t c0off;  // same for columns
+    int Px, Py, pi, pj;
+};
+struct GemmNoTail {};  // editions without a trailing kernel argument
+constexpr int gemm_log2(int x) { return x <= 1 ? 0 : 1 + gemm_log2(x / 2); }
+
+// Compile-time facts of one edition of k_dgemm_mfma:
+//   BM x 128 block tile, K-tiles of BK;
+//   TPB threads = TPB/64 waves as a (TPB/64/WN) x WN grid, each wave owning a
+//     64 x (16*FN) sub-tile as 4 x FN MFMA fragments;
+//   BT: B is stored N x K row-major (C -= A * B^T), not K x N;
+//   PERSIST: grid-stride loop over tiles, so the grid may be smaller than the
+//     tile count;
+//   MINB: minimum blocks per CU of the launch bounds;
+//   Tail: the kernel's last argument -- int = the non-temporal epilogue flag,
+//     TriMask = the lower-triangle early exit, GemmNoTail = none.
+// The editions are named types so that a trace shows which one ran.
+template <int BM_, int BK_, int TPB_, int WN_, int FN_, bool BT_,
+          bool PERSIST_, int MINB_, class Tail_>
+struct GemmCfg {
+    static constexpr int BM = BM_, BK = BK_, TPB = TPB_, WN = WN_, FN = FN_;
+    static constexpr int MINB = MINB_;
+    static constexpr bool BT = BT_, PERSIST = PERSIST_;
+    using Tail = Tail_;
+};
+// CONFLUX_GEMM_VARIANT=0: 4 waves (2x2) of 64x64.
+struct GemmW4 : GemmCfg<128, 16, 256, 2, 4, false, false, 1, GemmNoTail> {};
+// Variant 1, the default and the flop carrier of every factorization: 8 waves
+// (2x4) of 64x32.  NOTE (r02 measured): its launch bounds (512, 4) are
+// load-bearing -- they force a 128-register allocation (with a small scratch
+// spill) whose schedule sustains 57.7 TF; relaxing to (512, 2) (166 regs, no
+// spill, same 2-waves/SIMD occupancy) drops to 44.3, and software-pipelining
+// the fragment loads on top of it reaches only 45.  Keep the tight bound.
+struct GemmW8 : GemmCfg<128, 16, 512, 4, 2, false, true, 4, int> {};
+// Variant 3: 256x128 block tile, 8 waves as 4x2 of 64x64 -- double the
+// accumulator chains per wave and half the barriers per flop vs GemmW8; the
+// half-depth K-tile keeps it at 49.5 KB LDS -> 2 wg/CU.  Not persistent:
+// meant for the uncapped full-chip launches; the capped overlap path keeps
+// GemmW8.
+struct GemmBm256 : GemmCfg<256, 8, 512, 2, 4, false, false, 1, GemmNoTail> {};
+// NT edition of GemmW8: C -= A * B^T with B stored (N x K) row-major -- the
+// computeA11 low-rank update (reference Cholesky.cpp:345-351).
+struct GemmW8NT : GemmCfg<128, 16, 512, 4, 2, true, false, 4, TriMask> {};
+
+// Register-staged global->LDS with the write-after-barrier placement (guide
+// §5.5 T14), double-buffered, one barrier per K-step.
+template <class Cfg>
+__global__ __launch_bounds__(Cfg::TPB, Cfg::MINB) void k_dgemm_mfma(
     const double *__restrict__ A, int64_t lda, const double *__restrict__ B,
     int64_t ldb, double *__restrict__ C, int64_t ldc, int M, int64_t N, int K,
-    int ntm, int ntn, int strip_w) {
-    // bijective XCD swizzle (guide §5: q/r form)
-    int wg = blockIdx.x;
-    {
-        const int nwg = ntm * ntn;
-        const int q = nwg >> 3, r = nwg & 7;
-        const int xcd = wg & 7, idx = wg >> 3;
-        // inverse of dispatch round-robin: give each XCD a contiguous chunk
-        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-        if (nwg < 8) wg = blockIdx.x;   // tiny grids: identity
-    }
-    int tm, tn;
-    gemm_tile_of(wg, ntm, ntn, strip_w, tm, tn);
-    const int row0 = tm * GEMM_BM;
-    const int64_t col0 = (int64_t)tn * GEMM_BN;
+    int ntm, int ntn, int strip_w, typename Cfg::Tail tail) {
+    constexpr int BM = Cfg::BM, BN = GEMM_BN, BK = Cfg::BK, TPB = Cfg::TPB;
+    constexpr int WN = Cfg::WN, FN = Cfg::FN;
+    // staged elements per thread per K-tile: element e = tid + i*TPB of the
+    // BM*BK (A) or BK*BN (B) tile, so consecutive lanes read consecutive
+    // addresses along the BK-wide rows of A (and of an N x K B) or the
+    // BN-wide rows of a K x N B
+    constexpr int NA = BM * BK / TPB, NB = BK * BN / TPB;
+    // e is decoded with shifts and masks by the tile's row width (BK for A,
+    // BW for B): `/` and `%` by the same constants end as the same shifts
+    // but through other passes, and GemmW8's schedule is not the same after
+    // them (tools/isa_diff.py: its spill count changes)
+    constexpr int BW = Cfg::BT ? BK : BN;
+    constexpr int LBK = gemm_log2(BK), LBW = gemm_log2(BW);
+    constexpr bool NTC = std::is_same<typename Cfg::Tail, int>::value;
+    constexpr bool MASKED = std::is_same<typename Cfg::Tail, TriMask>::value;
+    static_assert(TPB / 64 / WN * 64 == BM && WN * FN * 16 == BN,
+                  "the wave grid must cover the block tile");
+    static_assert(NA * TPB == BM * BK && NB * TPB == BK * BN && BK % 4 == 0,
+                  "the K-tile must split evenly over threads and MFMA steps");
+    static_assert(1 << LBK == BK && 1 << LBW == BW, "powers of two");
 
-    __shared__ double As[2][GEMM_BK][GEMM_BM + 1];   // transposed, padded
-    __shared__ double Bs[2][GEMM_BK][GEMM_BN + 2];   // double-buffered
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int wm0 = (wave >> 1) * 64;             // wave's 64x64 sub-tile
-    const int wn0 = (wave & 1) * 64;
-    const int frow = lane & 15;                   // fragment row/col lane part
-    const int fk = lane >> 4;                     // fragment k lane part
-
-    f64x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f64x4{0, 0, 0, 0};
-
-    // staging registers: 8 A elements + 8 B elements per thread per K-tile
-    // (element e = tid + i*256 over the 2048-element tile; A reads coalesce
-    // over the 16-wide rows, B reads over the 128-wide rows)
-    double ra[8], rb[8];
-    const int ktiles = (K + GEMM_BK - 1) / GEMM_BK;
-
-    auto load_a = [&](int kt) {
-        const int kk = kt * GEMM_BK;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int e = tid + i * GEMM_TPB;          // 0..2047
-            const int r = e >> 4, k = e & 15;          // row-major in tile
-            const int gr = row0 + r;
-            ra[i] = (gr < M && kk + k < K) ? A[(int64_t)gr * lda + kk + k] : 0.0;
-        }
-    };
-    auto load_b = [&](int kt) {
-        const int kk = kt * GEMM_BK;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int e = tid + i * GEMM_TPB;          // 0..2047
-            const int k = e >> 7, c = e & 127;
-            const int64_t gc = col0 + c;
-            rb[i] = (kk + k < K && gc < N) ? B[(int64_t)(kk + k) * ldb + gc] : 0.0;
-        }
-    };
-    auto write_lds = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int e = tid + i * GEMM_TPB;
-            As[buf][e & 15][e >> 4] = ra[i];
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int e = tid + i * GEMM_TPB;
-            Bs[buf][e >> 7][e & 127] = rb[i];
-        }
-    };
-
-    load_a(0);
-    load_b(0);
-    write_lds(0);
-    __syncthreads();
-
-    int cur = 0;
-    for (int kt = 0; kt < ktiles; ++kt) {
-        if (kt + 1 < ktiles) {           // issue next tile's global loads
-            load_a(kt + 1);
-            load_b(kt + 1);
-        }
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const int k = kk * 4 + fk;
-            double af[4], bf[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) af[i] = As[cur][k][wm0 + i * 16 + frow];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bf[j] = Bs[cur][k][wn0 + j * 16 + frow];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(
-                        af[i], bf[j], acc[i][j], 0, 0, 0);
-        }
-        // write t+1 into the other buffer (everyone finished reading it at
-        // the barrier that ended step t-1), then one barrier per K-step
-        if (kt + 1 < ktiles) write_lds(cur ^ 1);
-        __syncthreads();
-        cur ^= 1;
-    }
-
-    // epilogue: C -= acc   (read-modify-write, coalesced over frag columns)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                // f64 16x16x4 C/D map (hardware-verified by mfma_probe):
-                // lane l, reg q -> D[4*q + (l>>4)][l & 15]
-                const int r = row0 + wm0 + i * 16 + q * 4 + fk;
-                const int64_t cidx = col0 + wn0 + j * 16 + frow;
-                if (r < M && cidx < N) {
-                    C[(int64_t)r * ldc + cidx] -= acc[i][j][q];
-                }
-            }
-        }
-    }
-}
-
-// NOTE (r02 measured): __launch_bounds__(512, 4) is load-bearing — it
-// forces a 128-register allocation (with a small scratch spill) whose
-// schedule sustains 57.7 TF; relaxing to (512, 2) (166 regs, no spill,
-// same 2-waves/SIMD occupancy) drops to 44.3, and software-pipelining the
-// fragment loads on top of it reaches only 45.  Keep the tight bound.
-__global__ __launch_bounds__(512, 4) void k_dgemm_f64_w8(
-    const double *__restrict__ A, int64_t lda, const double *__restrict__ B,
-    int64_t ldb, double *__restrict__ C, int64_t ldc, int M, int64_t N, int K,
-    int ntm, int ntn, int strip_w, int ntc) {
-    __shared__ double As[2][GEMM_BK][GEMM_BM + 1];   // transposed, padded
-    __shared__ double Bs[2][GEMM_BK][GEMM_BN + 2];   // double-buffered
-    const int nwg = ntm * ntn;
-    // persistent grid-stride over tiles: gridDim may be capped below nwg so
+    __shared__ double As[2][BK][BM + 1];   // transposed, padded
+    __shared__ double Bs[2][BK][BN + 2];   // double-buffered
+    // PERSIST: grid-stride over tiles.  gridDim may be capped below nwg so
     // the concurrent panel kernel (needs whole CUs: 135 KB LDS/block) can
     // co-schedule during lookahead.  gridDim == nwg -> one iteration,
-    // identical to the plain launch.
-    for (int vwg = blockIdx.x; vwg < nwg; vwg += gridDim.x) {
-    // bijective XCD swizzle (guide §5: q/r form)
+    // identical to the plain launch.  Otherwise: exactly one tile per block.
+    const int nwg = ntm * ntn;
+    for (int vwg = blockIdx.x; !Cfg::PERSIST || vwg < nwg; vwg += gridDim.x) {
+    // bijective XCD swizzle (guide §5: q/r form).  Written out here, not a
+    // helper shared with k_dgemm_f64_glds: as an inlined function it leaves
+    // GemmW8NT with other scalar registers (tools/isa_diff.py)
     int wg = vwg;
     {
         const int q = nwg >> 3, r = nwg & 7;
@@ -1524,59 +1474,74 @@ __global__ __launch_bounds__(512, 4) void k_dgemm_f64_w8(
     }
     int tm, tn;
     gemm_tile_of(wg, ntm, ntn, strip_w, tm, tn);
-    const int row0 = tm * GEMM_BM;
-    const int64_t col0 = (int64_t)tn * GEMM_BN;
+    const int row0 = tm * BM;
+    const int64_t col0 = (int64_t)tn * BN;
+    if constexpr (MASKED) {
+        if (tail.v > 0) {
+            const int gti =
+                (int)((tail.r0off + row0) / tail.v) * tail.Px + tail.pi;
+            const int gtj =
+                (int)((tail.c0off + col0) / tail.v) * tail.Py + tail.pj;
+            if (gti < gtj) return;  // above the global tile diagonal: untouched
+        }
+    }
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
-    const int wm0 = (wave >> 2) * 64;             // wave's 64x32 sub-tile
-    const int wn0 = (wave & 3) * 32;
+    const int wm0 = (wave / WN) * 64;             // wave's 64 x 16*FN sub-tile
+    const int wn0 = (wave % WN) * (16 * FN);
     const int frow = lane & 15;                   // fragment row/col lane part
     const int fk = lane >> 4;                     // fragment k lane part
 
-    f64x4 acc[4][2];
+    f64x4 acc[4][FN];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = f64x4{0, 0, 0, 0};
+        for (int j = 0; j < FN; ++j) acc[i][j] = f64x4{0, 0, 0, 0};
 
-    // staging registers: 8 A elements + 8 B elements per thread per K-tile
-    // (element e = tid + i*256 over the 2048-element tile; A reads coalesce
-    // over the 16-wide rows, B reads over the 128-wide rows)
-    double ra[4], rb[4];
-    const int ktiles = (K + GEMM_BK - 1) / GEMM_BK;
+    double ra[NA], rb[NB];                        // staging registers
+    const int ktiles = (K + BK - 1) / BK;
 
     auto load_a = [&](int kt) {
-        const int kk = kt * GEMM_BK;
+        const int kk = kt * BK;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int e = tid + i * 512;               // 0..2047
-            const int r = e >> 4, k = e & 15;          // row-major in tile
+        for (int i = 0; i < NA; ++i) {
+            const int e = tid + i * TPB;
+            const int r = e >> LBK, k = e & (BK - 1);  // row-major in tile
             const int gr = row0 + r;
             ra[i] = (gr < M && kk + k < K) ? A[(int64_t)gr * lda + kk + k] : 0.0;
         }
     };
     auto load_b = [&](int kt) {
-        const int kk = kt * GEMM_BK;
+        const int kk = kt * BK;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int e = tid + i * 512;               // 0..2047
-            const int k = e >> 7, c = e & 127;
-            const int64_t gc = col0 + c;
-            rb[i] = (kk + k < K && gc < N) ? B[(int64_t)(kk + k) * ldb + gc] : 0.0;
+        for (int i = 0; i < NB; ++i) {
+            const int e = tid + i * TPB;
+            // B's tile is row-major like B itself: K x N, or (BT) N x K,
+            // coalesced over k within each B row like the A staging
+            const int hi = e >> LBW, lo = e & (BW - 1);
+            const int k = Cfg::BT ? lo : hi;
+            const int64_t gc = col0 + (Cfg::BT ? hi : lo);
+            rb[i] = (kk + k < K && gc < N)
+                        ? (Cfg::BT ? B[gc * ldb + kk + k]
+                                   : B[(int64_t)(kk + k) * ldb + gc])
+                        : 0.0;
         }
     };
     auto write_lds = [&](int buf) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int e = tid + i * 512;
-            As[buf][e & 15][e >> 4] = ra[i];
+        for (int i = 0; i < NA; ++i) {
+            const int e = tid + i * TPB;
+            As[buf][e & (BK - 1)][e >> LBK] = ra[i];
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int e = tid + i * 512;
-            Bs[buf][e >> 7][e & 127] = rb[i];
+        for (int i = 0; i < NB; ++i) {
+            const int e = tid + i * TPB;
+            if constexpr (Cfg::BT)
+                Bs[buf][e & (BW - 1)][e >> LBW] = rb[i];
+            else
+                Bs[buf][e >> LBW][e & (BW - 1)] = rb[i];
         }
     };
 
@@ -1592,17 +1557,17 @@ __global__ __launch_bounds__(512, 4) void k_dgemm_f64_w8(
             load_b(kt + 1);
         }
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
+        for (int kk = 0; kk < BK / 4; ++kk) {
             const int k = kk * 4 + fk;
-            double af[4], bf[2];
+            double af[4], bf[FN];
 #pragma unroll
             for (int i = 0; i < 4; ++i) af[i] = As[cur][k][wm0 + i * 16 + frow];
 #pragma unroll
-            for (int j = 0; j < 2; ++j) bf[j] = Bs[cur][k][wn0 + j * 16 + frow];
+            for (int j = 0; j < FN; ++j) bf[j] = Bs[cur][k][wn0 + j * 16 + frow];
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j)
+                for (int j = 0; j < FN; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(
                         af[i], bf[j], acc[i][j], 0, 0, 0);
         }
@@ -1617,7 +1582,7 @@ __global__ __launch_bounds__(512, 4) void k_dgemm_f64_w8(
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
+        for (int j = 0; j < FN; ++j) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 // f64 16x16x4 C/D map (hardware-verified by mfma_probe):
@@ -1626,13 +1591,16 @@ __global__ __launch_bounds__(512, 4) void k_dgemm_f64_w8(
                 const int64_t cidx = col0 + wn0 + j * 16 + frow;
                 if (r < M && cidx < N) {
                     double *cp = &C[(int64_t)r * ldc + cidx];
-                    if (ntc) {
+                    if constexpr (NTC) {
                         // non-temporal RMW: C has zero reuse — keep its
                         // 4.3 GB/launch from evicting hot lines (the
                         // concurrent panel's sync slabs) out of the LLC
-                        __builtin_nontemporal_store(
-                            __builtin_nontemporal_load(cp) - acc[i][j][q],
-                            cp);
+                        if (tail)
+                            __builtin_nontemporal_store(
+                                __builtin_nontemporal_load(cp) - acc[i][j][q],
+                                cp);
+                        else
+                            *cp -= acc[i][j][q];
                     } else {
                         *cp -= acc[i][j][q];
                     }
@@ -1640,17 +1608,20 @@ __global__ __launch_bounds__(512, 4) void k_dgemm_f64_w8(
             }
         }
     }
+    if constexpr (!Cfg::PERSIST) return;
     // next tile re-stages buffer 0; the kt-loop's closing barrier already
     // ordered every wave's last LDS read before it
     if (vwg + gridDim.x < nwg) __syncthreads();
     }
 }
 
+
 // ---------------------------------------------------------------------------
 // fused inter-leaf glue of factor_panel: two launches per 32-column leaf in
-// place of gather + scatter + k_trsm_left_lower_unit32 + a K=32 k_dgemm_f64_w8.
-// No inter-block communication in either kernel; both reproduce the old
-// chain BIT FOR BIT (tests/test_panel_glue_gpu.py compares the two paths).
+// place of gather + scatter + k_trsm_left_lower_unit32 + a K=32
+// k_dgemm_mfma<GemmW8>.  No inter-block communication in either kernel; both
+// reproduce the old chain BIT FOR BIT (tests/test_panel_glue_gpu.py compares
+// the two paths).
 // ---------------------------------------------------------------------------
 // k_panel_glue_prep: thread = one column of [0, skip0) u [skip0 + 32,
 // tot_cols + 32), the columns launch_rowperm_skip covers at skipn = 32.  It
@@ -1730,12 +1701,12 @@ __global__ __launch_bounds__(64) void k_panel_glue_prep(
 
 // k_panel_glue_update: C (M x N) -= A (M x 32) * B (32 x N), K = 32 only.
 // One (64*WM) x (32*WN) tile per block, one 64 x 32 sub-tile per wave (the
-// w8 kernel's 4 x 2 fragments of v_mfma_f64_16x16x4_f64).  The whole K is
-// staged once (one barrier, no K loop) and the C tile is loaded into
+// GemmW8 edition's 4 x 2 fragments of v_mfma_f64_16x16x4_f64).  The whole K
+// is staged once (one barrier, no K loop) and the C tile is loaded into
 // registers BEFORE the staging writes and the MFMAs, so its HBM latency
 // overlaps them; then one subtraction and the store.  Bit-identity with
-// k_dgemm_f64_w8 at K = 32: accumulators start at zero, the eight k-blocks
-// of 4 run ascending with the same lane -> k map, then C = C - acc.
+// k_dgemm_mfma<GemmW8> at K = 32: accumulators start at zero, the eight
+// k-blocks of 4 run ascending with the same lane -> k map, then C = C - acc.
 // __launch_bounds__(.., 3): three 256-thread blocks a CU is what the 50 KB
 // of LDS admits, and under the concurrent trailing GEMM the kernel's share
 // of the memory system follows the bytes it keeps in flight.
@@ -1841,284 +1812,14 @@ __global__ __launch_bounds__(64 * WM * WN, 3) void k_panel_glue_update(
 }
 
 
-// 256x128 block-tile variant (CONFLUX_GEMM_VARIANT=3): 8 waves as 4x2 of
-// 64x64 fragments — double the accumulator chains per wave and half the
-// barriers per flop vs the 128x128 w8 kernel, at 99 KB LDS (1 wg/CU,
-// 2 waves/SIMD).  Plain (non-persistent) launch: meant for the uncapped
-// full-chip launches; the capped overlap path keeps the w8 kernel.
-__global__ __launch_bounds__(512) void k_dgemm_f64_bm256(
-    const double *__restrict__ A, int64_t lda, const double *__restrict__ B,
-    int64_t ldb, double *__restrict__ C, int64_t ldc, int M, int64_t N, int K,
-    int ntm, int ntn, int strip_w) {
-    int wg = blockIdx.x;
-    {
-        const int nwg = ntm * ntn;
-        const int q = nwg >> 3, r = nwg & 7;
-        const int xcd = wg & 7, idx = wg >> 3;
-        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-        if (nwg < 8) wg = blockIdx.x;
-    }
-    int tm, tn;
-    gemm_tile_of(wg, ntm, ntn, strip_w, tm, tn);
-    const int row0 = tm * 256;
-    const int64_t col0 = (int64_t)tn * GEMM_BN;
-
-    constexpr int BK8 = 8;  // half-depth K-tile: 49.5 KB LDS -> 2 wg/CU
-    __shared__ double As[2][BK8][256 + 1];   // transposed, padded
-    __shared__ double Bs[2][BK8][GEMM_BN + 2];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int wm0 = (wave >> 1) * 64;             // wave's 64x64 sub-tile
-    const int wn0 = (wave & 1) * 64;
-    const int frow = lane & 15;
-    const int fk = lane >> 4;
-
-    f64x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f64x4{0, 0, 0, 0};
-
-    double ra[4], rb[2];
-    const int ktiles = (K + BK8 - 1) / BK8;
-
-    auto load_a = [&](int kt) {
-        const int kk = kt * BK8;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int e = tid + i * 512;               // 0..2047
-            const int r = e >> 3, k = e & 7;
-            const int gr = row0 + r;
-            ra[i] = (gr < M && kk + k < K) ? A[(int64_t)gr * lda + kk + k] : 0.0;
-        }
-    };
-    auto load_b = [&](int kt) {
-        const int kk = kt * BK8;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int e = tid + i * 512;               // 0..1023
-            const int k = e >> 7, c = e & 127;
-            const int64_t gc = col0 + c;
-            rb[i] = (kk + k < K && gc < N) ? B[(int64_t)(kk + k) * ldb + gc] : 0.0;
-        }
-    };
-    auto write_lds = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int e = tid + i * 512;
-            As[buf][e & 7][e >> 3] = ra[i];
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int e = tid + i * 512;
-            Bs[buf][e >> 7][e & 127] = rb[i];
-        }
-    };
-
-    load_a(0);
-    load_b(0);
-    write_lds(0);
-    __syncthreads();
-
-    int cur = 0;
-    for (int kt = 0; kt < ktiles; ++kt) {
-        if (kt + 1 < ktiles) {
-            load_a(kt + 1);
-            load_b(kt + 1);
-        }
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const int k = kk * 4 + fk;
-            double af[4], bf[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) af[i] = As[cur][k][wm0 + i * 16 + frow];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bf[j] = Bs[cur][k][wn0 + j * 16 + frow];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(
-                        af[i], bf[j], acc[i][j], 0, 0, 0);
-        }
-        if (kt + 1 < ktiles) write_lds(cur ^ 1);
-        __syncthreads();
-        cur ^= 1;
-    }
-
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int r = row0 + wm0 + i * 16 + q * 4 + fk;
-                const int64_t cidx = col0 + wn0 + j * 16 + frow;
-                if (r < M && cidx < N) C[(int64_t)r * ldc + cidx] -= acc[i][j][q];
-            }
-        }
-    }
-}
-
-// NT variant: C -= A * B^T with B stored (N x K) row-major — the
-// computeA11 low-rank update (reference Cholesky.cpp:345-351).
-// Tile-cyclic lower-triangle mask (the Cholesky c4 single-launch update):
-// workgroups whose GLOBAL v-tile row < v-tile col exit immediately, so one
-// rectangular launch covers the trapezoid of tiles with i >= j and spends
-// nothing on the rest.  mask.v == 0 disables.  A 128-wide workgroup never
-// straddles a v-tile boundary (v % 128 == 0 enforced by the launcher).
-struct TriMask {
-    int v;          // global tile size (0 = no mask)
-    int r0off;      // launch-local row 0's offset within the rank-local A11
-    int64_t c0off;  // same for columns
-    int Px, Py, pi, pj;
-};
-
-__global__ __launch_bounds__(512, 4) void k_dgemm_f64_w8_nt(
-    const double *__restrict__ A, int64_t lda, const double *__restrict__ B,
-    int64_t ldb, double *__restrict__ C, int64_t ldc, int M, int64_t N, int K,
-    int ntm, int ntn, int strip_w, TriMask mask) {
-    // bijective XCD swizzle (guide §5: q/r form)
-    int wg = blockIdx.x;
-    {
-        const int nwg = ntm * ntn;
-        const int q = nwg >> 3, r = nwg & 7;
-        const int xcd = wg & 7, idx = wg >> 3;
-        // inverse of dispatch round-robin: give each XCD a contiguous chunk
-        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-        if (nwg < 8) wg = blockIdx.x;   // tiny grids: identity
-    }
-    int tm, tn;
-    gemm_tile_of(wg, ntm, ntn, strip_w, tm, tn);
-    const int row0 = tm * GEMM_BM;
-    const int64_t col0 = (int64_t)tn * GEMM_BN;
-    if (mask.v > 0) {
-        const int gti = (int)((mask.r0off + row0) / mask.v) * mask.Px + mask.pi;
-        const int gtj = (int)((mask.c0off + col0) / mask.v) * mask.Py + mask.pj;
-        if (gti < gtj) return;  // above the global tile diagonal: untouched
-    }
-
-    __shared__ double As[2][GEMM_BK][GEMM_BM + 1];   // transposed, padded
-    __shared__ double Bs[2][GEMM_BK][GEMM_BN + 2];   // double-buffered
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int wm0 = (wave >> 2) * 64;             // wave's 64x32 sub-tile
-    const int wn0 = (wave & 3) * 32;
-    const int frow = lane & 15;                   // fragment row/col lane part
-    const int fk = lane >> 4;                     // fragment k lane part
-
-    f64x4 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = f64x4{0, 0, 0, 0};
-
-    // staging registers: 8 A elements + 8 B elements per thread per K-tile
-    // (element e = tid + i*256 over the 2048-element tile; A reads coalesce
-    // over the 16-wide rows, B reads over the 128-wide rows)
-    double ra[4], rb[4];
-    const int ktiles = (K + GEMM_BK - 1) / GEMM_BK;
-
-    auto load_a = [&](int kt) {
-        const int kk = kt * GEMM_BK;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int e = tid + i * 512;               // 0..2047
-            const int r = e >> 4, k = e & 15;          // row-major in tile
-            const int gr = row0 + r;
-            ra[i] = (gr < M && kk + k < K) ? A[(int64_t)gr * lda + kk + k] : 0.0;
-        }
-    };
-    auto load_b = [&](int kt) {
-        // B is (N x K) row-major here: Bs[k][n] <- B[col0+n][kk+k]
-        // (coalesced over k within each B row, like the A staging)
-        const int kk = kt * GEMM_BK;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int e = tid + i * 512;               // 0..2047
-            const int n = e >> 4, k = e & 15;
-            const int64_t gc = col0 + n;
-            rb[i] = (kk + k < K && gc < N) ? B[gc * ldb + kk + k] : 0.0;
-        }
-    };
-    auto write_lds = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int e = tid + i * 512;
-            As[buf][e & 15][e >> 4] = ra[i];
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int e = tid + i * 512;
-            Bs[buf][e & 15][e >> 4] = rb[i];
-        }
-    };
-
-    load_a(0);
-    load_b(0);
-    write_lds(0);
-    __syncthreads();
-
-    int cur = 0;
-    for (int kt = 0; kt < ktiles; ++kt) {
-        if (kt + 1 < ktiles) {           // issue next tile's global loads
-            load_a(kt + 1);
-            load_b(kt + 1);
-        }
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const int k = kk * 4 + fk;
-            double af[4], bf[2];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) af[i] = As[cur][k][wm0 + i * 16 + frow];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) bf[j] = Bs[cur][k][wn0 + j * 16 + frow];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(
-                        af[i], bf[j], acc[i][j], 0, 0, 0);
-        }
-        // write t+1 into the other buffer (everyone finished reading it at
-        // the barrier that ended step t-1), then one barrier per K-step
-        if (kt + 1 < ktiles) write_lds(cur ^ 1);
-        __syncthreads();
-        cur ^= 1;
-    }
-
-    // epilogue: C -= acc   (read-modify-write, coalesced over frag columns)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                // f64 16x16x4 C/D map (hardware-verified by mfma_probe):
-                // lane l, reg q -> D[4*q + (l>>4)][l & 15]
-                const int r = row0 + wm0 + i * 16 + q * 4 + fk;
-                const int64_t cidx = col0 + wn0 + j * 16 + frow;
-                if (r < M && cidx < N) {
-                    C[(int64_t)r * ldc + cidx] -= acc[i][j][q];
-                }
-            }
-        }
-    }
-}
-
-
 // ---------------------------------------------------------------------------
 // glds variant: async global->LDS staging (__builtin_amdgcn_global_load_lds,
 // 16-byte pieces), one barrier per K-step, XOR-swizzled SOURCE addresses so
 // the lane-linear LDS image reads conflict-free (guide rule 21 / T2).
 // Layouts: As [BK][BM] row-of-m linear, A-chunk (row, p) stored at p^(row&7);
 //          Bs [BK][BN] linear, B-chunk (k, np) stored at np^((k&3)<<1).
-// Envelope (checked by launch_dgemm_f64, which runs k_dgemm_f64_w8 instead
-// when any of it fails): K % 16 == 0 (no K tail: a short last K-tile would
+// Envelope (checked by launch_dgemm_f64, which runs k_dgemm_mfma<GemmW8>
+// instead when any of it fails): K % 16 == 0 (no K tail: a short last K-tile would
 // read rows of B that do not exist), lda, ldb and N even and A, B 16-byte
 // aligned (every 16-byte piece is then aligned and lies wholly inside or
 // wholly outside the matrix).
@@ -2128,7 +1829,7 @@ __global__ __launch_bounds__(512, 4) void k_dgemm_f64_glds(
     int64_t ldb, double *__restrict__ C, int64_t ldc, int M, int64_t N, int K,
     int ntm, int ntn, int strip_w) {
     int wg = blockIdx.x;
-    {
+    {   // XCD swizzle, as in k_dgemm_mfma
         const int nwg = ntm * ntn;
         const int q = nwg >> 3, r = nwg & 7;
         const int xcd = wg & 7, idx = wg >> 3;
@@ -2142,11 +1843,12 @@ __global__ __launch_bounds__(512, 4) void k_dgemm_f64_glds(
 
     // ONE shared object (a second one makes hipcc drain vmcnt(0) before
     // every ds_read — guide §5 trap (a)).  [2 buffers][A 16*128 | B 16*128]
-    __shared__ double smem[2 * (GEMM_BK * GEMM_BM + GEMM_BK * GEMM_BN)];
-    double *As[2] = {smem, smem + 2 * GEMM_BK * GEMM_BM + 0};
     // carve: buf b: A at b*(BK*BM), B at 2*BK*BM + b*(BK*BN)
-    As[0] = smem;
-    As[1] = smem + GEMM_BK * GEMM_BM;
+    __shared__ double smem[2 * (GEMM_BK * GEMM_BM + GEMM_BK * GEMM_BN)];
+    // (through locals: an array initialised from `smem` directly becomes a
+    // static initialiser holding an LDS address, which does not compile)
+    double *As0 = smem;
+    double *As[2] = {As0, As0 + GEMM_BK * GEMM_BM};
     double *Bs0 = smem + 2 * GEMM_BK * GEMM_BM;
     double *Bs[2] = {Bs0, Bs0 + GEMM_BK * GEMM_BN};
 
@@ -2263,7 +1965,7 @@ __global__ __launch_bounds__(512, 4) void k_dgemm_f64_glds(
 // of LAPACKE_dpotrf('L') (Cholesky.cpp:192); the right/lower/trans TRSM is
 // k_trsm_right_tri32 with trans=1 (updateA10's dtrsm, Cholesky.cpp:280);
 // the NoTrans x Trans low-rank update (computeA11, Cholesky.cpp:345-351) is
-// k_dgemm_f64_w8_nt below.
+// k_dgemm_mfma<GemmW8NT> above.
 // ---------------------------------------------------------------------------
 // single block: in-place lower Cholesky of the nb x nb (nb <= 32) diagonal
 // block, row-major ld.  Sequential over columns in LDS (no pivoting).
@@ -3358,12 +3060,20 @@ void launch_getrf32_nopiv(double *A, int64_t lda, int nb, hipStream_t s) {
     hipLaunchKernelGGL(k_getrf32_nopiv, dim3(1), dim3(256), 0, s, A, lda, nb);
 }
 
-int g_dgemm_variant = -1;  // 0 = 4-wave, 1 = 8-wave; env CONFLUX_GEMM_VARIANT
-
-// process-global like g_dgemm_variant: the environment gives the default on
+// process-global GEMM launch switches: the environment gives the default on
 // first use, the setters below override it and return the previous value
+static int g_gemm_variant = -1;
 static int g_gemm_strip_w = -1;
 static int g_gemm_ntc = -1;
+
+// 0 = GemmW4, 1 = GemmW8, 2 = k_dgemm_f64_glds, 3 = GemmBm256
+static int gemm_variant() {
+    if (g_gemm_variant < 0) {
+        const char *e = getenv("CONFLUX_GEMM_VARIANT");
+        g_gemm_variant = e ? atoi(e) : 1;
+    }
+    return g_gemm_variant;
+}
 
 static int gemm_strip_w() {  // strip width in tiles; 0/1 = flat order
     if (g_gemm_strip_w < 0) {
@@ -3373,12 +3083,18 @@ static int gemm_strip_w() {  // strip width in tiles; 0/1 = flat order
     return g_gemm_strip_w;
 }
 
-static int gemm_ntc() {  // non-temporal C epilogue (w8 kernel)
+static int gemm_ntc() {  // non-temporal C epilogue (GemmW8)
     if (g_gemm_ntc < 0) {
         const char *e = getenv("CONFLUX_GEMM_NTC");
         g_gemm_ntc = e ? (atoi(e) != 0) : 0;
     }
     return g_gemm_ntc;
+}
+
+int conflux_gemm_set_variant(int variant) {
+    const int prev = gemm_variant();
+    g_gemm_variant = variant;
+    return prev;
 }
 
 int conflux_gemm_set_strip_w(int w) {
@@ -3394,7 +3110,7 @@ int conflux_gemm_set_ntc(int on) {
 }
 
 // k_dgemm_f64_glds stages whole 16-byte pieces and has no K tail: it may run
-// only inside this envelope.  Outside it variant 2 launches the w8 kernel.
+// only inside this envelope.  Outside it variant 2 launches GemmW8.
 static bool gemm_glds_ok(const double *A, int64_t lda, const double *B,
                          int64_t ldb, int64_t N, int K) {
     return K % GEMM_BK == 0 && lda % 2 == 0 && ldb % 2 == 0 && N % 2 == 0 &&
@@ -3405,34 +3121,29 @@ void launch_dgemm_f64(const double *A, int64_t lda, const double *B,
                       int64_t ldb, double *C, int64_t ldc, int M, int64_t N,
                       int K, hipStream_t s, int maxwg) {
     if (M <= 0 || N <= 0 || K <= 0) return;
-    if (g_dgemm_variant < 0) {
-        const char *e = getenv("CONFLUX_GEMM_VARIANT");
-        g_dgemm_variant = e ? atoi(e) : 1;
-    }
-    const int ntm = (int)cdiv64(M, GEMM_BM);
+    int variant = gemm_variant();
+    if (variant == 2 && !gemm_glds_ok(A, lda, B, ldb, N, K)) variant = 1;
+    const int ntm = (int)cdiv64(M, variant == 3 ? GemmBm256::BM : GEMM_BM);
     const int ntn = (int)cdiv64(N, GEMM_BN);
     const int sw = gemm_strip_w();
-    int variant = g_dgemm_variant;
-    if (variant == 2 && !gemm_glds_ok(A, lda, B, ldb, N, K)) variant = 1;
     int nwg = ntm * ntn;
-    // cap (persistent w8 kernel only): leave CUs free for a concurrent panel
+    // cap (persistent edition only): leave CUs free for a concurrent panel
     if (maxwg > 0 && variant == 1 && nwg > maxwg) nwg = maxwg;
-    if (variant == 3) {
-        const int ntm2 = (int)cdiv64(M, 256);
-        hipLaunchKernelGGL(k_dgemm_f64_bm256, dim3(ntm2 * ntn), dim3(512), 0,
-                           s, A, lda, B, ldb, C, ldc, M, N, K, ntm2, ntn, sw);
-        return;
-    }
-    if (variant == 2)
-        hipLaunchKernelGGL(k_dgemm_f64_glds, dim3(ntm * ntn), dim3(512), 0, s,
+    if (variant == 3)
+        hipLaunchKernelGGL(k_dgemm_mfma<GemmBm256>, dim3(nwg),
+                           dim3(GemmBm256::TPB), 0, s, A, lda, B, ldb, C, ldc,
+                           M, N, K, ntm, ntn, sw, GemmNoTail{});
+    else if (variant == 2)
+        hipLaunchKernelGGL(k_dgemm_f64_glds, dim3(nwg), dim3(512), 0, s,
                            A, lda, B, ldb, C, ldc, M, N, K, ntm, ntn, sw);
     else if (variant == 1)
-        hipLaunchKernelGGL(k_dgemm_f64_w8, dim3(nwg), dim3(512), 0, s,
-                           A, lda, B, ldb, C, ldc, M, N, K, ntm, ntn, sw,
+        hipLaunchKernelGGL(k_dgemm_mfma<GemmW8>, dim3(nwg), dim3(GemmW8::TPB),
+                           0, s, A, lda, B, ldb, C, ldc, M, N, K, ntm, ntn, sw,
                            gemm_ntc());
     else
-        hipLaunchKernelGGL(k_dgemm_f64, dim3(ntm * ntn), dim3(GEMM_TPB), 0, s,
-                           A, lda, B, ldb, C, ldc, M, N, K, ntm, ntn, sw);
+        hipLaunchKernelGGL(k_dgemm_mfma<GemmW4>, dim3(nwg), dim3(GemmW4::TPB),
+                           0, s, A, lda, B, ldb, C, ldc, M, N, K, ntm, ntn, sw,
+                           GemmNoTail{});
 }
 
 void launch_dgemm_f64_nt(const double *A, int64_t lda, const double *B,
@@ -3441,8 +3152,9 @@ void launch_dgemm_f64_nt(const double *A, int64_t lda, const double *B,
     if (M <= 0 || N <= 0 || K <= 0) return;
     const int ntm = (int)cdiv64(M, GEMM_BM);
     const int ntn = (int)cdiv64(N, GEMM_BN);
-    hipLaunchKernelGGL(k_dgemm_f64_w8_nt, dim3(ntm * ntn), dim3(512), 0, s, A,
-                       lda, B, ldb, C, ldc, M, N, K, ntm, ntn, gemm_strip_w(),
+    hipLaunchKernelGGL(k_dgemm_mfma<GemmW8NT>, dim3(ntm * ntn),
+                       dim3(GemmW8NT::TPB), 0, s, A, lda, B, ldb, C, ldc, M, N,
+                       K, ntm, ntn, gemm_strip_w(),
                        TriMask{0, 0, 0, 0, 0, 0, 0});
 }
 
@@ -3457,8 +3169,9 @@ void launch_dgemm_f64_nt_tril(const double *A, int64_t lda, const double *B,
     if (M <= 0 || N <= 0 || K <= 0) return;
     const int ntm = (int)cdiv64(M, GEMM_BM);
     const int ntn = (int)cdiv64(N, GEMM_BN);
-    hipLaunchKernelGGL(k_dgemm_f64_w8_nt, dim3(ntm * ntn), dim3(512), 0, s, A,
-                       lda, B, ldb, C, ldc, M, N, K, ntm, ntn, gemm_strip_w(),
+    hipLaunchKernelGGL(k_dgemm_mfma<GemmW8NT>, dim3(ntm * ntn),
+                       dim3(GemmW8NT::TPB), 0, s, A, lda, B, ldb, C, ldc, M, N,
+                       K, ntm, ntn, gemm_strip_w(),
                        TriMask{v, r0off, c0off, Px, Py, pi, pj});
 }
 

@@ -164,9 +164,8 @@ void launch_dgemm_f64(const double *A, int64_t lda, const double *B,
                       int K, hipStream_t s,
                       int maxwg = 0);
 // GEMM launch switches (CONFLUX_GEMM_VARIANT / _STRIP / _NTC give the
-// defaults; g_dgemm_variant < 0 = not read yet); the setters return the
-// previous value.
-extern int g_dgemm_variant;
+// defaults); the setters return the previous value.
+int conflux_gemm_set_variant(int variant);
 int conflux_gemm_set_strip_w(int w);
 int conflux_gemm_set_ntc(int on);
 void launch_pack_candidate(const double *A10, int64_t lda, const int *gri,

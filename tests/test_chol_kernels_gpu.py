@@ -1,9 +1,10 @@
 """The Cholesky / no-pivot kernel family, one launcher at a time, against the
 longdouble references and derived elementwise bounds of tests/_hp_ref.py:
-k_dgemm_f64_w8_nt with and without the TriMask, k_potrf32, k_getrf32_nopiv,
-k_trsm_right_upper32 and the blocked potrf_tile chain.  Operands sit in
-canvases of NaN canaries, and every kernel also runs a case built from exactly
-representable factors whose result must match bit for bit."""
+k_dgemm_mfma<GemmW8NT> with and without the TriMask, k_potrf32,
+k_getrf32_nopiv, k_trsm_right_upper32 and the blocked potrf_tile chain.
+Operands sit in canvases of NaN canaries, and every kernel also runs a case
+built from exactly representable factors whose result must match bit for
+bit."""
 import ctypes
 
 import numpy as np

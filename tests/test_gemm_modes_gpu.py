@@ -1,5 +1,6 @@
 """launch_dgemm_f64 in every mode it ships, against the longdouble reference
-and the derived elementwise bound of tests/_hp_ref.py: all four variants, the
+and the derived elementwise bound of tests/_hp_ref.py: all four variants (0, 1
+and 3 = k_dgemm_mfma<GemmW4>, <GemmW8>, <GemmBm256>; 2 = k_dgemm_f64_glds), the
 capped persistent loop, the strip tile order past its width, the XCD swizzle
 at nwg % 8 != 0, the non-temporal epilogue and leading dimensions that differ
 from the widths.  Operands sit in canvases of NaN canaries (nothing outside
@@ -158,8 +159,9 @@ def test_glds_inside_envelope(lib, M, N, K, ld):
     (128, 128, 8, "tight", True),     # the engine's v = 8: half a K-tile
 ])
 def test_glds_outside_envelope_runs_w8(lib, M, N, K, ld, even):
-    """Outside the envelope the launcher must run the w8 kernel: same bits as
-    variant 1, nothing read past the operands (the canaries are NaN)."""
+    """Outside the envelope the launcher must run k_dgemm_mfma<GemmW8>: same
+    bits as variant 1, nothing read past the operands (the canaries are
+    NaN)."""
     got = run(lib, 2, 0, M, N, K, ld, even=even)
     assert hp.bits_equal(got, run(lib, 1, 0, M, N, K, ld, even=even))
     assert ratio(got, M, N, K) <= 1.0
@@ -169,7 +171,7 @@ def test_glds_outside_envelope_runs_w8(lib, M, N, K, ld, even):
 
 def test_variant_is_restored(lib):
     """The selected variant holds for one call only: a plain debug_dgemm
-    afterwards gives the bits of the default (w8) kernel again."""
+    afterwards gives the bits of the default (GemmW8) kernel again."""
     M, N, K = 129, 257, 17
     A, B, C, _, _ = case(M, N, K)
     run(lib, 0, 0, M, N, K, "tight")

@@ -13,17 +13,28 @@ factorizations): the gap, the time inside it that is covered by each kernel
 family other than the capped trailing GEMM of the previous step, and the
 part of the gap in which none of those kernels runs ("idle": host work,
 launch latency, copies the trace does not show).  Trailing-GEMM launches
-(k_dgemm_f64_w8 with the capped grid) are reported separately because they
-overlap the stretch without being part of it.
+(k_dgemm_mfma<GemmW8>, in the table k_dgemm_f64_w8, with the capped grid) are
+reported separately because they overlap the stretch without being part of it.
 """
 import csv
 import sys
 from collections import defaultdict
 
 
+# the editions of k_dgemm_mfma<Cfg> are reported under the names these kernels
+# had before they became one template, so that traces from before and after,
+# and the tables in profiles/, read alike
+GEMM_EDITIONS = {"GemmW4": "k_dgemm_f64", "GemmW8": "k_dgemm_f64_w8",
+                 "GemmBm256": "k_dgemm_f64_bm256",
+                 "GemmW8NT": "k_dgemm_f64_w8_nt"}
+
+
 def short(name):
     n = name.split("(")[0].replace("void ", "").replace("ck::", "")
-    return n.split("<")[0]
+    base, _, args = n.partition("<")
+    if base == "k_dgemm_mfma":
+        return GEMM_EDITIONS.get(args.rstrip("> "), base)
+    return base
 
 
 def main(path, nt=32):
