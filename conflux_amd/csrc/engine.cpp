@@ -33,6 +33,7 @@
 #include "../../include/conflux_lu.h"
 #include "kernels.hpp"
 #include "norm1est.hpp"
+#include "pivot_push.hpp"
 
 #define HIPCHK(x)                                                       \
     do {                                                                \
@@ -55,6 +56,13 @@
     } while (0)
 
 namespace {
+
+// a process knob: the integer the environment gives `name`, `def` where it
+// is unset.  Callers that want it read once keep the result in a static.
+int env_int(const char *name, int def) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : def;
+}
 
 struct RankState {
     int pi = 0, pj = 0, pk = 0, grank = 0;
@@ -107,6 +115,21 @@ struct EvPair {
     double flops;
 };
 
+// the process knobs of the LU step, resolved once per factorization by
+// factor_loop (resolve_knobs); the step functions read nothing else
+struct Knobs {
+    bool split_trsm = true;  // CONFLUX_SPLIT_TRSM: the left solve on its own
+                             // stream (read once per process)
+    bool slice_trsm = true;  // CONFLUX_SLICE_TRSM: next panel's columns of
+                             // the left solve first (once per process)
+    bool lookahead = true;   // CONFLUX_LOOKAHEAD: next panel chain concurrent
+                             // with the trailing update (once per
+                             // factorization: tests set it between two)
+    int gemm_cap = 432;      // CONFLUX_GEMM_CAP: grid cap of the trailing
+                             // update under the look-ahead (once per process)
+    bool gap_stats = false;  // CONFLUX_GAP_STATS (once per process)
+};
+
 struct Ctx {
     int N = 0, v = 0, Px = 1, Py = 1, Pz = 1;
     int M = 0, Ml = 0, Nl = 0, Nt = 0, Mt = 0, nlayr = 0, tA11x = 0, tA11y = 0;
@@ -140,10 +163,25 @@ struct Ctx {
     unsigned epoch = 1;
     int direct = 0;              // one-rank direct bits of the factorization
                                  // in flight (ORD_*, set by factor_loop)
+    Knobs knobs;                 // same lifetime, same place
     std::vector<EvPair> evs;
     size_t evs_used = 0;
     TimeCat cats[4];
     std::string err;
+};
+
+// c.stream names the stream every helper enqueues on.  A region that runs on
+// another stream retargets it through this guard, which puts the previous
+// stream back on every exit, error returns included.
+struct StreamGuard {
+    Ctx &c;
+    hipStream_t saved;
+    StreamGuard(Ctx &c_, hipStream_t s) : c(c_), saved(c_.stream) {
+        c.stream = s;
+    }
+    ~StreamGuard() { c.stream = saved; }
+    StreamGuard(const StreamGuard &) = delete;
+    StreamGuard &operator=(const StreamGuard &) = delete;
 };
 
 inline int grank_of(const Ctx &c, int pi, int pj, int pk) {
@@ -229,11 +267,7 @@ int ev_end(Ctx &c, size_t slot) {
 // CONFLUX_NANCHECK=1 debug tracer: sync + sample a device buffer for
 // non-finite values, print tag.  Zero overhead when the env is unset.
 void nanscan(Ctx &c, const char *tag, int k, const double *p, int64_t nelem) {
-    static int on = -1;
-    if (on < 0) {
-        const char *e = getenv("CONFLUX_NANCHECK");
-        on = e ? atoi(e) : 0;
-    }
+    static const int on = env_int("CONFLUX_NANCHECK", 0);
     if (!on || !p || nelem <= 0) return;
     (void)hipStreamSynchronize(c.stream);
     const int64_t ns = std::min<int64_t>(nelem, 1 << 20);
@@ -272,10 +306,7 @@ void nanscan(Ctx &c, const char *tag, int k, const double *p, int64_t nelem) {
 // overrides it.
 int g_panel_glue = -1;
 int panel_glue_mode() {
-    if (g_panel_glue < 0) {
-        const char *e = getenv("CONFLUX_PANEL_GLUE");
-        g_panel_glue = e ? (atoi(e) != 0) : 1;
-    }
+    if (g_panel_glue < 0) g_panel_glue = env_int("CONFLUX_PANEL_GLUE", 1) != 0;
     return g_panel_glue;
 }
 
@@ -293,12 +324,23 @@ int factor_panel(Ctx &c, RankState &r, int n, std::vector<int> &ipiv_out) {
     ipiv_out.assign(v, 0);
     size_t slot;
     if (ev_begin(c, 1, 0, &slot)) return CONFLUX_LU_EHIP;
-    // one NB-wide leaf: persistent factor kernel + full-width rowperm (the
-    // factor kernel composed the realized sub-panel-relative permutation;
-    // applied in two parallel passes over the non-sub-panel columns)
-    auto leaf = [&](int jb, bool perm = true) -> int {
+    // A flat chain of NB-wide leaves.  (Two ablations that lost were taken
+    // out: a recursive xGETRF2-shaped glue and a capped glue grid, DESIGN.md
+    // section 9.)
+    const int glue = panel_glue_mode();
+    for (int jb = 0; jb < nsteps; jb += NB) {
         const int nb = std::min(NB, nsteps - jb);
         const int m = n - jb;  // rows of the sub-panel
+        // fused glue (CONFLUX_PANEL_GLUE, default 1): a full 32-column
+        // leaf with columns to its right and rows below it takes two
+        // purpose-built launches, bitwise equal to the four-launch
+        // chain below.  The last leaf of a panel (nothing to its right)
+        // uses the prep kernel for its permutation alone.  Ragged
+        // leaves and row-less updates stay on the chain.
+        const bool fused = glue && nb == 32 && jb + nb < v && m > nb;
+        const bool fused_perm = glue && nb == 32 && jb + nb == v && v > nb;
+        // the leaf: persistent factor kernel, which composes the realized
+        // sub-panel-relative permutation
         if (launch_panel_factor(r.panel + i64(jb) * v + jb, v, m, nb, r.sync,
                                 r.d_ipiv + jb, c.epoch, r.d_swap,
                                 r.d_swap + 64, c.stream)) {
@@ -306,105 +348,31 @@ int factor_panel(Ctx &c, RankState &r, int n, std::vector<int> &ipiv_out) {
             return CONFLUX_LU_EINTERNAL;
         }
         c.epoch += nb;
-        if (perm && v > nb)
+        if (fused || fused_perm) {
+            launch_panel_glue_prep(
+                r.panel, v, r.d_swap, r.d_swap + 64, jb, v - nb,
+                fused ? r.panel + i64(jb) * v + jb : nullptr, v, c.stream);
+        } else if (v > nb) {
+            // full-width rowperm, applied in two parallel passes over the
+            // non-sub-panel columns
             launch_rowperm_skip(r.panel, v, r.d_swap, r.d_swap + 64, jb,
                                 2 * nb, jb, nb, v - nb, r.rowtmp, c.stream);
-        return 0;
-    };
-    // MEASURED ABLATION (r02, default OFF): the recursion is numerically
-    // fine (all parity tests green) but SLOWER — 232.5 vs 223.5 ms/step
-    // in context, 150 vs 133 ms panel sequential at N=16384.  The fat-K
-    // node updates don't pay: node GEMMs are narrow (N = 32..256 cols →
-    // quarter-chip grids) where the flat chain's K=32 GEMMs span the full
-    // remaining width, and the h>=64 node TRSMs cost ~100-500 us each.
-    static int rec_env = -1;
-    if (rec_env < 0) {
-        const char *e = getenv("CONFLUX_PANEL_REC");
-        rec_env = e ? atoi(e) : 0;
-    }
-    const int nleaf = nsteps / NB;
-    if (rec_env && nsteps == v && v % NB == 0 && nleaf > 1 &&
-        (nleaf & (nleaf - 1)) == 0) {
-        // recursive right-looking glue (LAPACK xGETRF2 shape): leaves stay
-        // NB-wide, but the inter-leaf updates happen at power-of-two nodes
-        // as ONE rank-h TRSM + GEMM of the right half — the 15 K=32 glue
-        // GEMMs per 512-panel become 4 levels of K=32..256 MFMA passes.
-        // Row swaps stay eager full-width at the leaves, so operand rows
-        // are always fully permuted (laswp-both-sides equivalence).
-        int rc2 = 0;
-        std::function<void(int, int)> rec = [&](int a, int b) {
-            if (rc2) return;
-            if (b - a <= NB) {
-                rc2 = leaf(a);
-                return;
-            }
-            const int h = (b - a) / 2;
-            rec(a, a + h);
-            if (rc2) return;
-            // U block: rows a..a+h of cols a+h..b  (L of the left half)
-            if (h == 32)
-                launch_trsm_left_lower_unit32(r.panel + i64(a) * v + a, v,
-                                              r.panel + i64(a) * v + a + h, v,
-                                              h, b - a - h, c.stream);
-            else
-                launch_trsm_left_mfma(r.panel + i64(a) * v + a, v,
-                                      r.panel + i64(a) * v + a + h, v, h,
-                                      b - a - h, c.stream);
-            if (n > a + h)
-                launch_dgemm_f64(r.panel + i64(a + h) * v + a, v,
-                                 r.panel + i64(a) * v + a + h, v,
-                                 r.panel + i64(a + h) * v + a + h, v,
-                                 n - (a + h), b - a - h, h, c.stream);
-            rec(a + h, b);
-        };
-        rec(0, v);
-        if (rc2) return rc2;
-    } else {
-        const int glue = panel_glue_mode();
-        for (int jb = 0; jb < nsteps; jb += NB) {
-            const int nb = std::min(NB, nsteps - jb);
-            const int m = n - jb;
-            // fused glue (CONFLUX_PANEL_GLUE, default 1): a full 32-column
-            // leaf with columns to its right and rows below it takes two
-            // purpose-built launches, bitwise equal to the four-launch
-            // chain below.  The last leaf of a panel (nothing to its right)
-            // uses the prep kernel for its permutation alone.  Ragged
-            // leaves and row-less updates stay on the chain.
-            const bool fused = glue && nb == 32 && jb + nb < v && m > nb;
-            const bool fused_perm =
-                glue && nb == 32 && jb + nb == v && v > nb;
-            if (leaf(jb, !(fused || fused_perm))) return CONFLUX_LU_EINTERNAL;
-            if (fused || fused_perm)
-                launch_panel_glue_prep(
-                    r.panel, v, r.d_swap, r.d_swap + 64, jb, v - nb,
-                    fused ? r.panel + i64(jb) * v + jb : nullptr, v,
-                    c.stream);
-            if (fused) {
-                launch_panel_glue_update(r.panel + i64(jb + nb) * v + jb, v,
-                                         r.panel + i64(jb) * v + jb + nb, v,
-                                         r.panel + i64(jb + nb) * v + jb + nb,
-                                         v, m - nb, v - jb - nb, c.stream);
-            } else if (jb + nb < v && m > nb) {
-                // U block: rows jb..jb+nb of cols jb+nb..v
-                launch_trsm_left_lower_unit32(r.panel + i64(jb) * v + jb, v,
-                                              r.panel + i64(jb) * v + jb + nb,
-                                              v, nb, v - jb - nb, c.stream);
-                // trailing sub-panel update.  CONFLUX_GLUE_CAP (measured
-                // ablation, default 0 = uncapped): a small persistent
-                // glue grid (48/64/96) measures 222/213/210 ms/step vs
-                // 199.5 uncapped — the full-grid launch's wave churn
-                // through the free slots beats holding them
-                static int glue_cap = -1;
-                if (glue_cap < 0) {
-                    const char *gc = getenv("CONFLUX_GLUE_CAP");
-                    glue_cap = gc ? atoi(gc) : 0;
-                }
-                launch_dgemm_f64(r.panel + i64(jb + nb) * v + jb, v,
-                                 r.panel + i64(jb) * v + jb + nb, v,
-                                 r.panel + i64(jb + nb) * v + jb + nb, v,
-                                 m - nb, v - jb - nb, nb, c.stream,
-                                 glue_cap);
-            }
+        }
+        if (fused) {
+            launch_panel_glue_update(r.panel + i64(jb + nb) * v + jb, v,
+                                     r.panel + i64(jb) * v + jb + nb, v,
+                                     r.panel + i64(jb + nb) * v + jb + nb, v,
+                                     m - nb, v - jb - nb, c.stream);
+        } else if (jb + nb < v && m > nb) {
+            // U block: rows jb..jb+nb of cols jb+nb..v
+            launch_trsm_left_lower_unit32(r.panel + i64(jb) * v + jb, v,
+                                          r.panel + i64(jb) * v + jb + nb, v,
+                                          nb, v - jb - nb, c.stream);
+            // trailing sub-panel update on the full grid
+            launch_dgemm_f64(r.panel + i64(jb + nb) * v + jb, v,
+                             r.panel + i64(jb) * v + jb + nb, v,
+                             r.panel + i64(jb + nb) * v + jb + nb, v, m - nb,
+                             v - jb - nb, nb, c.stream, 0);
         }
     }
     if (ev_end(c, slot)) return CONFLUX_LU_EHIP;
@@ -458,10 +426,8 @@ void ipiv_to_perm(const std::vector<int> &ipiv, int n, int v,
 // Process-global; conflux_lu_debug_set_trsm_stripe overrides it.
 int g_trsm_stripe = -1;
 int trsm_stripe_mode() {
-    if (g_trsm_stripe < 0) {
-        const char *e = getenv("CONFLUX_TRSM_STRIPE");
-        g_trsm_stripe = e ? (atoi(e) != 0) : 1;
-    }
+    if (g_trsm_stripe < 0)
+        g_trsm_stripe = env_int("CONFLUX_TRSM_STRIPE", 1) != 0;
     return g_trsm_stripe;
 }
 
@@ -518,10 +484,9 @@ int fused_trsm_left(RankState &r, double *X, int64_t ldx, int v, int64_t N,
 enum { ORD_SOLVES = 1, ORD_PUSH = 2, ORD_DEAD = 4, ORD_ALL = 7 };
 int g_one_rank_direct = -1;
 int one_rank_direct_mode() {
-    if (g_one_rank_direct < 0) {
-        const char *e = getenv("CONFLUX_ONE_RANK_DIRECT");
-        g_one_rank_direct = e ? (atoi(e) & ORD_ALL) : ORD_ALL;
-    }
+    if (g_one_rank_direct < 0)
+        g_one_rank_direct =
+            env_int("CONFLUX_ONE_RANK_DIRECT", ORD_ALL) & ORD_ALL;
     return g_one_rank_direct;
 }
 // the bits in force on this engine; bit 1 needs the stripe solves
@@ -844,6 +809,8 @@ struct StepPlan {
     std::vector<int> gpivots;                    // v
     std::vector<std::vector<int>> lrows;         // per pi: global rows
     std::vector<std::vector<int>> order;         // per pi: pivot-order slots
+    int n_early0 = 0;  // rank 0's early count of the push, for the sliced
+                       // push's second part
 };
 
 // g2lnoTile (conflux_opt.cpp:74-98)
@@ -865,22 +832,43 @@ int run_step(Ctx &c, int k, StepPlan &sp);
 // chains, accumulated over run_step calls and printed to stderr after each
 // factorization: run_step entry -> first TRSM enqueue, the gri/igri update
 // alone, run_step entry -> the ev_pc record.  Off by default (no clock reads).
+using GapClock = std::chrono::steady_clock;
 struct GapStats {
     double to_trsm = 0, gri = 0, to_evpc = 0;
     long steps = 0, evpc_steps = 0;
+    GapClock::time_point t0;  // entry of the step in flight
 };
 GapStats g_gap;
-bool gap_stats_on() {
-    static int on = -1;
-    if (on < 0) {
-        const char *e = getenv("CONFLUX_GAP_STATS");
-        on = e ? atoi(e) != 0 : 0;
-    }
-    return on != 0;
-}
-using GapClock = std::chrono::steady_clock;
 inline double gap_ms(GapClock::time_point a, GapClock::time_point b) {
     return std::chrono::duration<double, std::milli>(b - a).count();
+}
+
+// The knobs of the factorization about to start.  CONFLUX_LOOKAHEAD is read
+// here, once per factorization; the others keep their first value for the
+// life of the process.
+Knobs resolve_knobs() {
+    static const int split = env_int("CONFLUX_SPLIT_TRSM", 1);
+    // CONFLUX_SLICE_TRSM HISTORY: off by default from r02 to r06.  With r02's
+    // fused TRSM, which streamed all previously-solved 32-wide L panels
+    // through LDS once PER LAUNCH whatever the X width, the split nearly
+    // tripled the solve cost (trsm 33 -> 65 ms/job) and the step was slower
+    // (229.6 vs 201 ms at N=16384).  The r05 stripe solves are
+    // width-proportional: re-measured in r07 (profiles/r07_leaf_body_ab.log)
+    // the split costs 7 ms of solve time (trsm 22.5 -> 29.5 ms/job) and the
+    // step is 5-6 ms FASTER in every alternated pair, so it is on by default
+    // (CONFLUX_SLICE_TRSM=0 turns it off).  Same pivots either way.
+    static const int slice = env_int("CONFLUX_SLICE_TRSM", 1);
+    // r02 re-sweep with 256-row panel blocks: 432 ~= 400 (201.5 ms) > 448 >
+    // 464 at N=16384
+    static const int cap = env_int("CONFLUX_GEMM_CAP", 432);
+    static const int gap = env_int("CONFLUX_GAP_STATS", 0);
+    Knobs kn;
+    kn.split_trsm = split != 0;
+    kn.slice_trsm = slice != 0;
+    kn.lookahead = env_int("CONFLUX_LOOKAHEAD", 1) != 0;
+    kn.gemm_cap = cap;
+    kn.gap_stats = gap != 0;
+    return kn;
 }
 
 int factor_loop(Ctx &c, double *elapsed_ms) {
@@ -905,6 +893,7 @@ int factor_loop(Ctx &c, double *elapsed_ms) {
     for (auto &t : c.cats) t = TimeCat{};
     g_gap = GapStats{};
     c.direct = one_rank_direct_bits(c);
+    c.knobs = resolve_knobs();
 
     int rc = timed_region(c, elapsed_ms, [&]() -> int {
         StepPlan sp;
@@ -917,11 +906,7 @@ int factor_loop(Ctx &c, double *elapsed_ms) {
         return 0;
     });
     if (rc) return rc;
-    static int spin_stats = -1;
-    if (spin_stats < 0) {
-        const char *e = getenv("CONFLUX_SPIN_STATS");
-        spin_stats = e ? atoi(e) : 0;
-    }
+    static const int spin_stats = env_int("CONFLUX_SPIN_STATS", 0);
     if (spin_stats) {
         for (auto &r : c.rs) {
             unsigned long long sp2 = 0;
@@ -941,7 +926,7 @@ int factor_loop(Ctx &c, double *elapsed_ms) {
         for (auto &x : g_panel_phase_acc) x = 0;
         g_panel_phase_cols = 0;
     }
-    if (gap_stats_on())
+    if (c.knobs.gap_stats)
         std::fprintf(stderr,
                      "[gapstats] steps=%ld entry->trsm=%.3f ms  gri/igri=%.3f "
                      "ms  entry->ev_pc=%.3f ms (%ld steps)\n",
@@ -950,74 +935,122 @@ int factor_loop(Ctx &c, double *elapsed_ms) {
     return 0;
 }
 
-int phase01(Ctx &c, int k, StepPlan &sp) {
-    const int v = c.v, Px = c.Px, Py = c.Py, Pz = c.Pz;
-    const int64_t Nl = c.Nl;
-    const int loff = (k / Py) * v;
-    const int kcol = k % Py, krow = k % Px;
-    const int n_rounds = Px > 1 ? (int)std::ceil(std::log2((double)Px)) : 0;
+// Geometry and mode of superstep k, computed once per step (make_step) from
+// the grid, c.direct and c.knobs; no step function decides any of it again.
+struct Step {
+    int k = 0;
+    int loff = 0;         // local column of the panel's block
+    int kcol = 0, krow = 0;
+    int64_t wA01 = 0;     // columns loff..Nl
+    bool look = false;    // a step k+1 exists
+    int ncol = 0;         // its process column
+    int64_t lnext = 0;    // its local column
+    // the two panel solves run on two streams (steps 4 & 5)
+    bool split_trsm = false;
+    // degenerate 1-rank grid: solve the v columns step k+1's panel needs
+    // FIRST and record ev_t5a after them, so the (a) GEMM and the next panel
+    // chain start without waiting for the rest of the A01 solve.  Only where
+    // the next panel may run concurrently: in sequential mode
+    // (CONFLUX_LOOKAHEAD=0) nothing waits for the slice and the split costs
+    // its 7 ms for nothing.
+    bool slice_first = false;
+    // one-rank direct path (c.direct, see one_rank_direct_mode): direct =
+    // the solves read A11 and write the Rcv buffers, nothing is staged in
+    // A10 / A01pack / A01; sliced = only columns [loff, lnext + v) of A11 are
+    // pushed before ev_t3, the rest on the solve stream behind the slice
+    // solve; dead = the panel's own column block [loff, loff + v) is neither
+    // solved for nor updated.  Stream and hazard argument: DESIGN.md section 1.
+    bool direct = false, sliced = false;
+    int64_t dead = 0;
+    int64_t wfirst = 0;   // columns from loff pushed and packed before ev_t3
+};
 
-    // one-rank direct: the column block goes straight into the panel and A10
-    // is not written (its only readers are the push, the right solve and the
-    // slab spread of the staged path)
-    const bool direct = c.direct & ORD_SOLVES;
+Step make_step(const Ctx &c, int k) {
+    Step s;
+    s.k = k;
+    s.loff = (k / c.Py) * c.v;
+    s.kcol = k % c.Py;
+    s.krow = k % c.Px;
+    s.wA01 = c.Nl - s.loff;
+    s.look = k + 1 < c.Nt;
+    s.ncol = (k + 1) % c.Py;
+    s.lnext = i64(c.v) * ((k + 1) / c.Py);
+    s.split_trsm = !c.sim && c.trsm_stream && c.knobs.split_trsm;
+    s.slice_first = s.split_trsm && c.knobs.slice_trsm && c.Pz == 1 &&
+                    c.Px == 1 && s.look && c.panel_stream && c.knobs.lookahead;
+    s.direct = c.direct & ORD_SOLVES;
+    s.sliced = (c.direct & ORD_PUSH) && s.slice_first;
+    s.dead = (c.direct & ORD_DEAD) ? c.v : 0;
+    s.wfirst = s.sliced ? s.lnext + c.v - s.loff : s.wA01;
+    return s;
+}
 
-    // ---- step 0: copy active col block to A10, depth-reduce (C1) ----------
+// ---- steps 0 and 1: the panel chain (phase01) -----------------------------
+
+// dgetrf contract violated (ipiv[i] outside [i, n)): scan the panel input for
+// non-finite data and say what was found
+int ipiv_range_error(Ctx &c, RankState &r, int k, int i, int piv, int n) {
+    std::vector<double> samp(i64(std::min(n, 4096)) * c.v);
+    (void)hipMemcpy(samp.data(), r.panel, samp.size() * 8,
+                    hipMemcpyDeviceToHost);
+    long bad = 0;
+    for (double x : samp)
+        if (!std::isfinite(x)) ++bad;
+    c.err = "panel ipiv out of range: k=" + std::to_string(k) +
+            " i=" + std::to_string(i) + " ipiv=" + std::to_string(piv) +
+            " n=" + std::to_string(n) + " nonfinite=" + std::to_string(bad) +
+            "/" + std::to_string(samp.size()) +
+            " panel[0]=" + std::to_string(samp[0]);
+    return CONFLUX_LU_EINTERNAL;
+}
+
+// step 0: copy the active column block to A10, depth-reduce (C1).  One-rank
+// direct: the column block goes straight into the panel and A10 is not
+// written (its only readers are the push, the right solve and the slab
+// spread of the staged path).
+int reduce_panel_column(Ctx &c, const Step &st) {
+    if (st.direct) return 0;
+    const int v = c.v;
     for (auto &r : c.rs) {
-        if (r.pj != kcol || direct) continue;
-        launch_copy2d(r.A11 + i64(r.fnp) * Nl + loff, Nl,
+        if (r.pj != st.kcol) continue;
+        launch_copy2d(r.A11 + i64(r.fnp) * c.Nl + st.loff, c.Nl,
                       r.A10 + i64(r.fnp) * v, v, r.nact, v, c.stream);
     }
-    if (!direct) {
-        // the panel chain's comm (it may overlap main-stream exchanges);
-        // fnp/nact are the same on every rank of a rank row
-        std::vector<ReduceItem> items;
-        for (auto &r : c.rs)
-            if (r.pj == kcol && (r.pk == 0 || !c.sim))
-                items.push_back({r.pi, kcol, i64(r.nact) * v,
-                                 [v](RankState &x) {
-                                     return x.A10 + i64(x.fnp) * v;
-                                 }});
-        if (depth_reduce(c, c.pcomm, items)) return CONFLUX_LU_ECOMM;
-    }
+    // the panel chain's comm (it may overlap main-stream exchanges);
+    // fnp/nact are the same on every rank of a rank row
+    std::vector<ReduceItem> items;
+    for (auto &r : c.rs)
+        if (r.pj == st.kcol && (r.pk == 0 || !c.sim))
+            items.push_back({r.pi, st.kcol, i64(r.nact) * v,
+                             [v](RankState &x) {
+                                 return x.A10 + i64(x.fnp) * v;
+                             }});
+    return depth_reduce(c, c.pcomm, items) ? CONFLUX_LU_ECOMM : 0;
+}
 
-    // ---- step 1: tournament pivoting --------------------------------------
-    sp.gpivots.assign(v, -1);
-    std::vector<int> perm;
+// step 1, local part: big LUP on every rank's reduced column panel
+// (conflux_opt.hpp:727), then either the result itself (Px == 1) or the
+// winners as round-0 candidates
+int factor_local_panels(Ctx &c, const Step &st, StepPlan &sp, int n_rounds) {
+    const int v = c.v, k = st.k;
+    std::vector<int> perm, ipiv;
     for (auto &r : c.rs) {
-        if (r.pj != kcol || r.pk != 0) continue;
+        if (r.pj != st.kcol || r.pk != 0) continue;
         const int n = r.nact;
-        // big LUP on the reduced column panel (conflux_opt.hpp:727)
-        if (direct)
-            launch_copy2d(r.A11 + i64(r.fnp) * Nl + loff, Nl, r.panel, v, n, v,
-                          c.stream);
+        if (st.direct)
+            launch_copy2d(r.A11 + i64(r.fnp) * c.Nl + st.loff, c.Nl, r.panel,
+                          v, n, v, c.stream);
         else
             launch_copy2d(r.A10 + i64(r.fnp) * v, v, r.panel, v, n, v,
                           c.stream);
-        std::vector<int> ipiv;
+        ipiv.clear();
         if (n > 0) {
             if (factor_panel(c, r, n, ipiv)) return CONFLUX_LU_EINTERNAL;
             // dgetrf contract: ipiv[i] in [i, n) — catches any kernel-side
             // pivot corruption before it can index out of bounds below
             for (int i = 0; i < std::min(v, n); ++i)
-                if (ipiv[i] < i || ipiv[i] >= n) {
-                    // diagnose: scan the panel input for non-finite data
-                    std::vector<double> samp(i64(std::min(n, 4096)) * v);
-                    (void)hipMemcpy(samp.data(), r.panel, samp.size() * 8,
-                                    hipMemcpyDeviceToHost);
-                    long bad = 0;
-                    double a0 = samp[0];
-                    for (double x : samp)
-                        if (!std::isfinite(x)) ++bad;
-                    c.err = "panel ipiv out of range: k=" +
-                            std::to_string(k) + " i=" + std::to_string(i) +
-                            " ipiv=" + std::to_string(ipiv[i]) +
-                            " n=" + std::to_string(n) +
-                            " nonfinite=" + std::to_string(bad) + "/" +
-                            std::to_string(samp.size()) +
-                            " panel[0]=" + std::to_string(a0);
-                    return CONFLUX_LU_EINTERNAL;
-                }
+                if (ipiv[i] < i || ipiv[i] >= n)
+                    return ipiv_range_error(c, r, k, i, ipiv[i], n);
         }
         ipiv_to_perm(ipiv, n, v, perm);
         if (n == 0) std::iota(perm.begin(), perm.end(), 0);
@@ -1026,10 +1059,11 @@ int phase01(Ctx &c, int k, StepPlan &sp) {
             // Px == 1 (reference gap; intent): A00 = top v x v of factors,
             // gpivots = candidate col 0 gathered by perm — all host-side
             launch_copy2d(r.panel, v, r.A00, v, std::min(v, n), v, c.stream);
-            if (direct && pack_step_triangles(c, r, k)) return CONFLUX_LU_EHIP;
+            if (st.direct && pack_step_triangles(c, r, k))
+                return CONFLUX_LU_EHIP;
             for (int i = 0; i < v; ++i)
                 sp.gpivots[i] = (perm[i] < n) ? r.gri[r.fnp + perm[i]] : 0;
-            if (!c.sim && c.world > 1)  // feed the C4 broadcast below
+            if (!c.sim && c.world > 1)  // feed the C4 broadcast
                 HIPCHK(hipMemcpyAsync(r.d_gpivots, sp.gpivots.data(), v * 4,
                                       hipMemcpyHostToDevice, c.stream));
         } else {
@@ -1037,17 +1071,23 @@ int phase01(Ctx &c, int k, StepPlan &sp) {
             // top/bottom by the round-0 pairing (conflux_opt.hpp:724,741-751)
             HIPCHK(hipMemcpyAsync(r.d_perm, perm.data(), v * 4,
                                   hipMemcpyHostToDevice, c.stream));
-            const int part0 = std::min(r.pi ^ 1, Px - 1);
+            const int part0 = std::min(r.pi ^ 1, c.Px - 1);
             const int64_t off = (part0 < r.pi) ? i64(v) * (v + 1) : 0;
             launch_pack_candidate(r.A10, v, r.d_gri, r.fnp, n, v, v, r.d_perm,
                                   r.cand + off, c.stream);
         }
     }
+    return 0;
+}
 
+// step 1, the tournament: per round, exchange halves with the butterfly
+// partner (C2) and factor the merged 2v x v candidate
+int tournament_rounds(Ctx &c, const Step &st, int n_rounds) {
+    const int v = c.v, kcol = st.kcol;
+    const int64_t half = i64(v) * (v + 1);
+    std::vector<int> perm, ipiv;
     for (int rd = 0; rd < n_rounds; ++rd) {
-        // exchange halves (C2): each pair (lo,hi) ends with
-        // [lo winners ; hi winners]
-        const int64_t half = i64(v) * (v + 1);
+        // each pair (lo,hi) ends with [lo winners ; hi winners]
         if (!c.sim) {
             RankState &me = c.rs[0];
             if (me.pj == kcol && me.pk == 0) {
@@ -1062,7 +1102,7 @@ int phase01(Ctx &c, int k, StepPlan &sp) {
                 NCCLCHK(ncclGroupEnd());
             }
         } else {
-            for (int pi = 0; pi < Px; ++pi) {
+            for (int pi = 0; pi < c.Px; ++pi) {
                 const int src = pi ^ (1 << rd);
                 if (src < pi) continue;  // handle each pair once
                 RankState &lo = *get_rs(c, pi, kcol, 0);
@@ -1077,169 +1117,116 @@ int phase01(Ctx &c, int k, StepPlan &sp) {
             if (r.pj != kcol || r.pk != 0) continue;
             // LUP on the merged 2v x v candidate (cols 1..v+1)
             launch_copy2d(r.cand + 1, v + 1, r.panel, v, 2 * v, v, c.stream);
-            std::vector<int> ipiv;
             if (factor_panel(c, r, 2 * v, ipiv)) return CONFLUX_LU_EINTERNAL;
             ipiv_to_perm(ipiv, 2 * v, v, perm);
             HIPCHK(hipMemcpyAsync(r.d_perm, perm.data(), v * 4,
                                   hipMemcpyHostToDevice, c.stream));
+            launch_row_gather(r.cand, v + 1, r.rowtmp, v + 1, r.d_perm, v,
+                              v + 1, c.stream);
             if (rd == n_rounds - 1) {
-                launch_row_gather(r.cand, v + 1, r.rowtmp, v + 1, r.d_perm, v,
-                                  v + 1, c.stream);
-                if (d2d(c, r.cand, r.rowtmp, i64(v) * (v + 1)))
-                    return CONFLUX_LU_EHIP;
+                if (d2d(c, r.cand, r.rowtmp, half)) return CONFLUX_LU_EHIP;
                 launch_copy2d(r.panel, v, r.A00, v, v, v, c.stream);
             } else {
                 const int nxt = r.pi ^ (1 << (rd + 1));
                 const int64_t off = (nxt < r.pi) ? half : 0;
-                launch_row_gather(r.cand, v + 1, r.rowtmp, v + 1, r.d_perm, v,
-                                  v + 1, c.stream);
-                if (d2d(c, r.cand + off, r.rowtmp, half)) return CONFLUX_LU_EHIP;
+                if (d2d(c, r.cand + off, r.rowtmp, half))
+                    return CONFLUX_LU_EHIP;
             }
         }
     }
-
-    if (n_rounds > 0 || (!c.sim && c.world > 1)) {
-        // extract gpivots from candidate col 0 (conflux_opt.hpp:810-816)
-        if (n_rounds > 0)
-            for (auto &r : c.rs) {
-                if (r.pj != kcol || r.pk != 0) continue;
-                launch_extract_col0_int(r.cand, v + 1, v, r.d_gpivots,
-                                        c.stream);
-            }
-        // A00 transpose-pair exchange (C3) + gpivots broadcast (C4)
-        if (!c.sim) {
-            RankState &me = c.rs[0];
-            NCCLCHK(ncclGroupStart());
-            if (me.pj == kcol && me.pk == 0 &&
-                !(me.pi == krow && me.pj == kcol)) {
-                NCCLCHK(ncclSend(me.A00, i64(v) * v, ncclDouble,
-                                 grank_of(c, krow, me.pi, 0), c.pcomm,
-                                 c.stream));
-            }
-            if (me.pi == krow && me.pk == 0 &&
-                !(me.pj == kcol)) {
-                NCCLCHK(ncclRecv(me.A00, i64(v) * v, ncclDouble,
-                                 grank_of(c, me.pj, kcol, 0), c.pcomm,
-                                 c.stream));
-            }
-            // gpivots: root (pi, kcol, 0) -> its jk plane
-            if (me.pj == kcol && me.pk == 0) {
-                for (int pj = 0; pj < Py; ++pj)
-                    for (int pk = 0; pk < Pz; ++pk) {
-                        if (pj == kcol && pk == 0) continue;
-                        NCCLCHK(ncclSend(me.d_gpivots, v, ncclInt32,
-                                         grank_of(c, me.pi, pj, pk), c.pcomm,
-                                         c.stream));
-                    }
-            } else {
-                NCCLCHK(ncclRecv(me.d_gpivots, v, ncclInt32,
-                                 grank_of(c, me.pi, kcol, 0), c.pcomm,
-                                 c.stream));
-            }
-            NCCLCHK(ncclGroupEnd());
-            HIPCHK(hipMemcpyAsync(sp.gpivots.data(), me.d_gpivots, v * 4,
-                                  hipMemcpyDeviceToHost, c.stream));
-            HIPCHK(hipStreamSynchronize(c.stream));
-        } else {
-            // all participants hold identical winners; A00 lands on row krow
-            RankState &part = *get_rs(c, 0, kcol, 0);
-            HIPCHK(hipMemcpyAsync(sp.gpivots.data(), part.d_gpivots, v * 4,
-                                  hipMemcpyDeviceToHost, c.stream));
-            for (int pi = 0; pi < Px; ++pi)
-                for (int pj = 0; pj < Py; ++pj) {
-                    RankState &dst = *get_rs(c, pi, pj, 0);
-                    if (pi == krow && pj != kcol)
-                        if (d2d(c, dst.A00, part.A00, i64(v) * v))
-                            return CONFLUX_LU_EHIP;
-                }
-            HIPCHK(hipStreamSynchronize(c.stream));
-        }
-    }
-
-    plan_from_gpivots(c, sp);
-    std::copy_n(sp.gpivots.begin(), v, c.pivotInds.begin() + i64(k) * v);
     return 0;
 }
 
-// steps 2..6 of superstep k; sp holds this step's pivot plan (from phase01).
-// At the tail, the trailing update is split so that the columns of step
-// k+1's panel are updated FIRST, and phase01(k+1) runs on the panel stream
-// CONCURRENTLY with the rest of the trailing update (lookahead — numerically
-// identical: the column split does not reorder any K-sum).  On exit sp holds
-// step k+1's plan.
-int run_step(Ctx &c, int k, StepPlan &sp) {
-    const int v = c.v, Px = c.Px, Py = c.Py, Pz = c.Pz;
-    const int64_t Nl = c.Nl;
-    const int loff = (k / Py) * v;
-    const int kcol = k % Py, krow = k % Px;
-    const int64_t wA01 = Nl - loff;
-    const bool look = (k + 1 < c.Nt);
-    const int ncol = (k + 1) % Py;
-    const int64_t lnext = i64(v) * ((k + 1) / Py);
-    const bool gap_on = gap_stats_on();
-    GapClock::time_point gap_t0;
-    if (gap_on) gap_t0 = GapClock::now();
+// after the tournament: gpivots out of candidate col 0
+// (conflux_opt.hpp:810-816), A00 transpose-pair exchange (C3), gpivots
+// broadcast (C4), and the download that ends the chain in a host sync
+int exchange_a00_gpivots(Ctx &c, const Step &st, StepPlan &sp, int n_rounds) {
+    const int v = c.v, kcol = st.kcol, krow = st.krow;
+    if (n_rounds > 0)
+        for (auto &r : c.rs) {
+            if (r.pj != kcol || r.pk != 0) continue;
+            launch_extract_col0_int(r.cand, v + 1, v, r.d_gpivots, c.stream);
+        }
+    if (!c.sim) {
+        RankState &me = c.rs[0];
+        NCCLCHK(ncclGroupStart());
+        if (me.pj == kcol && me.pk == 0 && !(me.pi == krow && me.pj == kcol))
+            NCCLCHK(ncclSend(me.A00, i64(v) * v, ncclDouble,
+                             grank_of(c, krow, me.pi, 0), c.pcomm, c.stream));
+        if (me.pi == krow && me.pk == 0 && !(me.pj == kcol))
+            NCCLCHK(ncclRecv(me.A00, i64(v) * v, ncclDouble,
+                             grank_of(c, me.pj, kcol, 0), c.pcomm, c.stream));
+        // gpivots: root (pi, kcol, 0) -> its jk plane
+        if (me.pj == kcol && me.pk == 0) {
+            for (int pj = 0; pj < c.Py; ++pj)
+                for (int pk = 0; pk < c.Pz; ++pk) {
+                    if (pj == kcol && pk == 0) continue;
+                    NCCLCHK(ncclSend(me.d_gpivots, v, ncclInt32,
+                                     grank_of(c, me.pi, pj, pk), c.pcomm,
+                                     c.stream));
+                }
+        } else {
+            NCCLCHK(ncclRecv(me.d_gpivots, v, ncclInt32,
+                             grank_of(c, me.pi, kcol, 0), c.pcomm, c.stream));
+        }
+        NCCLCHK(ncclGroupEnd());
+        HIPCHK(hipMemcpyAsync(sp.gpivots.data(), me.d_gpivots, v * 4,
+                              hipMemcpyDeviceToHost, c.stream));
+    } else {
+        // all participants hold identical winners; A00 lands on row krow
+        RankState &part = *get_rs(c, 0, kcol, 0);
+        HIPCHK(hipMemcpyAsync(sp.gpivots.data(), part.d_gpivots, v * 4,
+                              hipMemcpyDeviceToHost, c.stream));
+        for (int pi = 0; pi < c.Px; ++pi)
+            for (int pj = 0; pj < c.Py; ++pj)
+                if (pi == krow && pj != kcol)
+                    if (d2d(c, get_rs(c, pi, pj, 0)->A00, part.A00,
+                            i64(v) * v))
+                        return CONFLUX_LU_EHIP;
+    }
+    HIPCHK(hipStreamSynchronize(c.stream));
+    return 0;
+}
 
-    // the two panel solves run on two streams (steps 4 & 5 below); decided
-    // here because the one-rank direct path shapes its row push by it
-    static int split_env = -1;
-    if (split_env < 0) {
-        const char *se = getenv("CONFLUX_SPLIT_TRSM");
-        split_env = se ? atoi(se) : 1;
-    }
-    const bool split_trsm = !c.sim && c.trsm_stream && split_env;
-    // degenerate 1-rank grid: solve the v columns step k+1's panel needs
-    // FIRST and record ev_t5a after them, so the (a) GEMM and the next
-    // panel chain start without waiting for the rest of the A01 solve.
-    // HISTORY: off by default from r02 to r06.  With r02's fused TRSM, which
-    // streamed all previously-solved 32-wide L panels through LDS once PER
-    // LAUNCH whatever the X width, the split nearly tripled the solve cost
-    // (trsm 33 -> 65 ms/job) and the step was slower (229.6 vs 201 ms at
-    // N=16384).  The r05 stripe solves are width-proportional: re-measured in
-    // r07 (profiles/r07_leaf_body_ab.log) the split costs 7 ms of solve time
-    // (trsm 22.5 -> 29.5 ms/job) and the step is 5-6 ms FASTER in every
-    // alternated pair, so it is on by default (CONFLUX_SLICE_TRSM=0 turns
-    // it off).  Same pivots either way.
-    static int slice_env = -1;
-    if (slice_env < 0) {
-        const char *se2 = getenv("CONFLUX_SLICE_TRSM");
-        slice_env = se2 ? atoi(se2) : 1;
-    }
-    // (only where the next panel runs concurrently, the condition of
-    // async_look below: in sequential mode, CONFLUX_LOOKAHEAD=0, nothing
-    // waits for the slice and the split costs its 7 ms for nothing)
-    const char *lk_slice = getenv("CONFLUX_LOOKAHEAD");
-    const bool slice_first =
-        split_trsm && slice_env && Pz == 1 && Px == 1 && look &&
-        c.panel_stream && (lk_slice ? atoi(lk_slice) != 0 : true);
-    // one-rank direct path (c.direct, see one_rank_direct_mode): direct =
-    // the solves read A11 and write the Rcv buffers, nothing is staged in
-    // A10 / A01pack / A01; sliced = only columns [loff, lnext + v) of A11 are
-    // pushed before ev_t3, the rest on the solve stream behind the slice
-    // solve; dead = the panel's own column block [loff, loff + v) is neither
-    // solved for nor updated.  Stream and hazard argument: DESIGN.md section 1.
-    const bool direct = c.direct & ORD_SOLVES;
-    const bool sliced = (c.direct & ORD_PUSH) && slice_first;
-    const int64_t dead = (c.direct & ORD_DEAD) ? v : 0;
-    const int64_t wfirst = sliced ? lnext + v - loff : wA01;  // before ev_t3
-    // rows that move, one column window [col0, col0 + cols) of mat at a
-    // time: pivot rows to rowtmp, early rows down to the late positions,
-    // pivot rows to [f, f + cnt) (d_idx as uploaded below)
-    auto push_rows = [&](RankState &r, double *mat, int64_t ld, int64_t col0,
-                         int64_t cols, int f, int cnt, int n_early) -> int {
-        size_t slot;
-        if (ev_begin(c, 3, 0, &slot)) return CONFLUX_LU_EHIP;
-        launch_row_gather(mat + col0, ld, r.rowtmp, cols, r.d_idx, cnt, cols,
-                          c.stream);
-        launch_row_move(mat + col0, ld, mat + col0, ld, r.d_idx + v,
-                        r.d_idx + 2 * v, n_early, cols, c.stream);
-        launch_copy2d(r.rowtmp, cols, mat + i64(f) * ld + col0, ld, cnt, cols,
+// steps 0 and 1 of superstep k on c.stream: on return sp holds its pivot plan
+int phase01(Ctx &c, int k, StepPlan &sp) {
+    const Step st = make_step(c, k);
+    const int n_rounds =
+        c.Px > 1 ? (int)std::ceil(std::log2((double)c.Px)) : 0;
+    sp.gpivots.assign(c.v, -1);
+    if (int rc = reduce_panel_column(c, st)) return rc;
+    if (int rc = factor_local_panels(c, st, sp, n_rounds)) return rc;
+    if (int rc = tournament_rounds(c, st, n_rounds)) return rc;
+    if (n_rounds > 0 || (!c.sim && c.world > 1))
+        if (int rc = exchange_a00_gpivots(c, st, sp, n_rounds)) return rc;
+    plan_from_gpivots(c, sp);
+    std::copy_n(sp.gpivots.begin(), c.v, c.pivotInds.begin() + i64(k) * c.v);
+    return 0;
+}
+
+// ---- steps 2..6 (run_step) ------------------------------------------------
+
+// rows that move, one column window [col0, col0 + cols) of mat at a time:
+// pivot rows to rowtmp, early rows down to the late positions, pivot rows to
+// [f, f + cnt) (d_idx as uploaded by push_pivot_rows)
+int push_rows(Ctx &c, RankState &r, double *mat, int64_t ld, int64_t col0,
+              int64_t cols, int f, int cnt, int n_early) {
+    const int v = c.v;
+    size_t slot;
+    if (ev_begin(c, 3, 0, &slot)) return CONFLUX_LU_EHIP;
+    launch_row_gather(mat + col0, ld, r.rowtmp, cols, r.d_idx, cnt, cols,
                       c.stream);
-        return ev_end(c, slot);
-    };
-    int n_early0 = 0;  // rank 0's count, for the sliced push's second part
+    launch_row_move(mat + col0, ld, mat + col0, ld, r.d_idx + v,
+                    r.d_idx + 2 * v, n_early, cols, c.stream);
+    launch_copy2d(r.rowtmp, cols, mat + i64(f) * ld + col0, ld, cnt, cols,
+                  c.stream);
+    return ev_end(c, slot);
+}
 
-    // ---- step 2: push pivot rows up, pack, depth-reduce (C7) --------------
+// step 2: push pivot rows up, pack, depth-reduce (C7)
+int push_pivot_rows(Ctx &c, const Step &st, StepPlan &sp) {
+    const int v = c.v, k = st.k;
+    const int64_t Nl = c.Nl;
     for (auto &r : c.rs) {
         const auto &lr = sp.lrows[r.pi];
         const auto &ord = sp.order[r.pi];
@@ -1253,11 +1240,6 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
         int *const stage = r.h_idx + (k & 1) * 4 * v;
         int *const lrows_loc = stage, *const early = stage + v,
                    *const late = stage + 2 * v;
-        // host work proportional to the rows that move, not to Ml: only
-        // positions [f, f+cnt) and the pivot rows' own positions matter
-        const int wend = std::min(f + cnt, c.Ml);
-        std::vector<char> in_win(std::max(wend - f, 0), 0);
-        int n_early = 0, n_late = 0;
         for (int i = 0; i < cnt; ++i) {
             const int p = (lr[i] >= 0 && lr[i] < c.M) ? r.igri[lr[i]] : -1;
             if (p < 0) {
@@ -1268,16 +1250,10 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
             }
             lrows_loc[i] = p;
             stage[3 * v + i] = ord[i];
-            if (p >= f && p < wend)
-                in_win[p - f] = 1;
-            else if (p >= f + cnt)
-                late[n_late++] = p;
         }
-        std::sort(late, late + n_late);
-        n_late = (int)(std::unique(late, late + n_late) - late);
-        for (int i = f; i < wend; ++i)
-            if (!in_win[i - f]) early[n_early++] = i;
-        if (n_early != n_late) {
+        int n_early = 0, n_late = 0;
+        if (pivot_push::lists(lrows_loc, cnt, f, c.Ml, early, late, &n_early,
+                              &n_late)) {
             std::set<int> uniq(lr.begin(), lr.end());
             c.err = "pivot push invariant: k=" + std::to_string(k) +
                     " cnt=" + std::to_string(cnt) +
@@ -1290,112 +1266,56 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
         if (cnt)
             HIPCHK(hipMemcpyAsync(r.d_idx, stage, size_t(4) * v * 4,
                                   hipMemcpyHostToDevice, c.stream));
-        auto push = [&](double *mat, int64_t ld, int64_t col0,
-                        int64_t cols) -> int {
-            return push_rows(r, mat, ld, col0, cols, f, cnt, n_early);
-        };
-        n_early0 = n_early;
+        sp.n_early0 = n_early;
         // (sliced: columns left of loff are not read again)
-        if (sliced ? push(r.A11, Nl, loff, wfirst) : push(r.A11, Nl, 0, Nl))
+        if (st.sliced ? push_rows(c, r, r.A11, Nl, st.loff, st.wfirst, f, cnt,
+                                  n_early)
+                      : push_rows(c, r, r.A11, Nl, 0, Nl, f, cnt, n_early))
             return CONFLUX_LU_EHIP;
-        if (!direct && push(r.A10, v, 0, v)) return CONFLUX_LU_EHIP;
-        if (c.store_factors && push(r.A10hist, Nl, 0, Nl))
+        if (!st.direct && push_rows(c, r, r.A10, v, 0, v, f, cnt, n_early))
+            return CONFLUX_LU_EHIP;
+        if (c.store_factors &&
+            push_rows(c, r, r.A10hist, Nl, 0, Nl, f, cnt, n_early))
             return CONFLUX_LU_EHIP;
         // host gri/igri update (identical shuffle)
-        {
-            GapClock::time_point gri_t0;
-            if (gap_on) gri_t0 = GapClock::now();
-            std::vector<int> tmp(cnt);
-            for (int i = 0; i < cnt; ++i) tmp[i] = r.gri[lrows_loc[i]];
-            for (int i = 0; i < n_late; ++i) {
-                r.gri[late[i]] = r.gri[early[i]];
-                r.igri[r.gri[late[i]]] = late[i];
-            }
-            for (int i = 0; i < cnt; ++i) {
-                r.gri[f + i] = tmp[i];
-                r.igri[tmp[i]] = f + i;
-            }
-            // d_gri's only device reader is the tournament's candidate pack
-            // (phase01, grids with Px > 1); positions outside [f, last late
-            // row] did not change
-            if (Px > 1 && cnt) {
-                const int hi = n_late ? late[n_late - 1] + 1 : f + cnt;
-                HIPCHK(hipMemcpyAsync(r.d_gri + f, r.gri.data() + f,
-                                      size_t(hi - f) * 4,
-                                      hipMemcpyHostToDevice, c.stream));
-            }
-            if (gap_on) g_gap.gri += gap_ms(gri_t0, GapClock::now());
+        GapClock::time_point gri_t0;
+        if (c.knobs.gap_stats) gri_t0 = GapClock::now();
+        pivot_push::apply(r.gri.data(), r.igri.data(), lrows_loc, cnt, f,
+                          early, late, n_late);
+        // d_gri's only device reader is the tournament's candidate pack
+        // (factor_local_panels, grids with Px > 1); positions outside [f,
+        // last late row] did not change
+        if (c.Px > 1 && cnt) {
+            const int hi = n_late ? late[n_late - 1] + 1 : f + cnt;
+            HIPCHK(hipMemcpyAsync(r.d_gri + f, r.gri.data() + f,
+                                  size_t(hi - f) * 4, hipMemcpyHostToDevice,
+                                  c.stream));
         }
+        if (c.knobs.gap_stats) g_gap.gri += gap_ms(gri_t0, GapClock::now());
         r.fnp += cnt;
         r.nact -= cnt;
         // pack pivot rows cols loff.. for the depth reduce
-        if (!direct)
-            launch_copy2d(r.A11 + i64(f) * Nl + loff, Nl, r.A01pack, wA01, cnt,
-                          wfirst, c.stream);
+        if (!st.direct)
+            launch_copy2d(r.A11 + i64(f) * Nl + st.loff, Nl, r.A01pack,
+                          st.wA01, cnt, st.wfirst, c.stream);
     }
-    {
-        std::vector<ReduceItem> items;
-        for (int pi = 0; pi < Px; ++pi)
-            for (int pj = 0; pj < Py; ++pj)
-                items.push_back({pi, pj, i64(sp.lrows[pi].size()) * wA01,
-                                 [](RankState &x) { return x.A01pack; }});
-        if (depth_reduce(c, c.comm, items)) return CONFLUX_LU_ECOMM;
-    }
+    std::vector<ReduceItem> items;
+    for (int pi = 0; pi < c.Px; ++pi)
+        for (int pj = 0; pj < c.Py; ++pj)
+            items.push_back({pi, pj, i64(sp.lrows[pi].size()) * st.wA01,
+                             [](RankState &x) { return x.A01pack; }});
+    return depth_reduce(c, c.comm, items) ? CONFLUX_LU_ECOMM : 0;
+}
 
-    // ---- step 3: route packed pivot rows to row krow, pivot-ordered (C5/C6)
-    if (direct) {
-        // the left solve reads the pivot rows where the push left them
-    } else if (!c.sim) {
-        RankState &me = c.rs[0];
-        if (me.pk == 0) {
-            NCCLCHK(ncclGroupStart());
-            if (me.pi != krow) {
-                const int cnt = (int)sp.lrows[me.pi].size();
-                if (cnt)
-                    NCCLCHK(ncclSend(me.A01pack, i64(cnt) * wA01, ncclDouble,
-                                     grank_of(c, krow, me.pj, 0), c.comm,
-                                     c.stream));
-            } else {
-                int64_t off = 0;
-                for (int pi = 0; pi < Px; ++pi) {
-                    if (pi == krow) continue;
-                    const int cnt = (int)sp.lrows[pi].size();
-                    if (cnt)
-                        NCCLCHK(ncclRecv(me.redtmp + off, i64(cnt) * wA01,
-                                         ncclDouble, grank_of(c, pi, me.pj, 0),
-                                         c.comm, c.stream));
-                    off += i64(cnt) * wA01;
-                }
-            }
-            NCCLCHK(ncclGroupEnd());
-            if (me.pi == krow) {
-                // scatter own + received rows into A01 by pivot order
-                const int cnt_own = (int)sp.lrows[krow].size();
-                if (cnt_own) {
-                    HIPCHK(hipMemcpyAsync(me.d_idx + 3 * v,
-                                          sp.order[krow].data(), cnt_own * 4,
-                                          hipMemcpyHostToDevice, c.stream));
-                    launch_row_scatter(me.A01pack, wA01, me.A01, wA01,
-                                       me.d_idx + 3 * v, cnt_own, wfirst,
-                                       c.stream);
-                }
-                int64_t off = 0;
-                for (int pi = 0; pi < Px; ++pi) {
-                    if (pi == krow) continue;
-                    const int cnt = (int)sp.lrows[pi].size();
-                    if (cnt) {
-                        HIPCHK(hipMemcpyAsync(me.d_idx, sp.order[pi].data(),
-                                              cnt * 4, hipMemcpyHostToDevice,
-                                              c.stream));
-                        launch_row_scatter(me.redtmp + off, wA01, me.A01, wA01,
-                                           me.d_idx, cnt, wA01, c.stream);
-                    }
-                    off += i64(cnt) * wA01;
-                }
-            }
-        }
-    } else {
-        for (int pj = 0; pj < Py; ++pj) {
+// step 3: route packed pivot rows to row krow, pivot-ordered (C5/C6).
+// One-rank direct: nothing, the left solve reads the pivot rows where the
+// push left them.
+int route_pivot_rows(Ctx &c, const Step &st, StepPlan &sp) {
+    if (st.direct) return 0;
+    const int v = c.v, Px = c.Px, krow = st.krow;
+    const int64_t wA01 = st.wA01;
+    if (c.sim) {
+        for (int pj = 0; pj < c.Py; ++pj) {
             RankState &dst = *get_rs(c, krow, pj, 0);
             for (int pi = 0; pi < Px; ++pi) {
                 RankState &src = *get_rs(c, pi, pj, 0);
@@ -1407,181 +1327,226 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
                                    cnt, wA01, c.stream);
             }
         }
-    }
-
-    // ---- store_factors: ship this step's pivot rows' L history (C10) ------
-    if (c.store_factors && k > 0) {
-        const int ltik = k / Px;  // local row-tile of global tile k on row krow
-        for (int pj = 0; pj < Py; ++pj) {
-            const int64_t histcols =
-                i64(v) * (pj < kcol ? k / Py + 1 : k / Py);
-            if (histcols == 0) continue;
-            for (int pi = 0; pi < Px; ++pi) {
-                const int cnt = (int)sp.lrows[pi].size();
-                if (!cnt) continue;
-                RankState *src = get_rs(c, pi, pj, 0);
-                RankState *dst = get_rs(c, krow, pj, 0);
-                if (c.sim) {
-                    HIPCHK(hipMemcpyAsync(dst->d_idx + 2 * v,
-                                          sp.order[pi].data(), cnt * 4,
-                                          hipMemcpyHostToDevice, c.stream));
-                    // src hist rows fnp-cnt..fnp (post-push) -> dst Fres rows
-                    // ltik*v + order[i]
-                    launch_row_scatter(
-                        src->A10hist + i64(src->fnp - cnt) * Nl, Nl,
-                        dst->Fres + i64(ltik) * v * Nl, Nl, dst->d_idx + 2 * v,
-                        cnt, histcols, c.stream);
-                } else {
-                    RankState &me = c.rs[0];
-                    if (src && src->grank == me.grank && dst &&
-                        dst->grank == me.grank) {
-                        // (sliced: the second part of the A11 push still
-                        // needs the late list at d_idx + 2v; the order list
-                        // of this one rank row is already at d_idx + 3v)
-                        int *const d_ord = me.d_idx + (sliced ? 3 : 2) * v;
-                        if (!sliced)
-                            HIPCHK(hipMemcpyAsync(d_ord, sp.order[pi].data(),
-                                                  cnt * 4,
-                                                  hipMemcpyHostToDevice,
-                                                  c.stream));
-                        launch_row_scatter(me.A10hist + i64(me.fnp - cnt) * Nl,
-                                           Nl, me.Fres + i64(ltik) * v * Nl,
-                                           Nl, d_ord, cnt, histcols,
-                                           c.stream);
-                    } else if (src && src->grank == me.grank) {
-                        launch_copy2d(me.A10hist + i64(me.fnp - cnt) * Nl, Nl,
-                                      me.rowtmp, histcols, cnt, histcols,
-                                      c.stream);
-                        NCCLCHK(ncclSend(me.rowtmp, i64(cnt) * histcols,
-                                         ncclDouble,
-                                         grank_of(c, krow, pj, 0), c.comm,
-                                         c.stream));
-                    } else if (dst && dst->grank == me.grank) {
-                        NCCLCHK(ncclRecv(me.rowtmp, i64(cnt) * histcols,
-                                         ncclDouble, grank_of(c, pi, pj, 0),
-                                         c.comm, c.stream));
-                        HIPCHK(hipMemcpyAsync(me.d_idx + 2 * v,
-                                              sp.order[pi].data(), cnt * 4,
-                                              hipMemcpyHostToDevice, c.stream));
-                        launch_row_scatter(me.rowtmp, histcols,
-                                           me.Fres + i64(ltik) * v * Nl, Nl,
-                                           me.d_idx + 2 * v, cnt, histcols,
-                                           c.stream);
-                    }
-                }
-            }
-        }
-    }
-
-    // ---- steps 4 & 5 compute: the two panel TRSMs are independent after
-    // step 3 — run the step-5 TRSM on the second stream concurrently with
-    // the step-4 TRSM (the spreads below stay ordered on the main stream,
-    // C8 overlapping the step-5 solve like the reference's Iscatterv window,
-    // conflux_opt.hpp:1424-1615).
-    // store_factors: the solved U rows (and the diagonal tile) go to Fres,
-    // on whichever stream the solve ran
-    auto store_u = [&](RankState &r) {
-        if (!c.store_factors) return;
-        double *Frow = r.Fres + i64(k / Px) * v * Nl;  // local row tile of k
-        // U region starts at this rank's first local column tile with
-        // global tile >= k; columns left of it carry stale already-factored
-        // data the reference never reads (cf. oracle lu_oracle.py step-5
-        // `gcs >= off` mask)
-        // (dead: the diagonal tile's columns were not solved for; A00 below)
-        const int64_t ustart =
-            i64(v) * (r.pj < kcol ? k / Py + 1 : k / Py) + dead;
-        if (Nl - ustart > 0 && direct)
-            launch_copy2d(r.A01Rcv + (ustart - loff), Nl, Frow + ustart, Nl, v,
-                          Nl - ustart, c.stream);
-        else if (Nl - ustart > 0)
-            launch_copy2d(r.A01 + (ustart - loff), wA01, Frow + ustart, Nl, v,
-                          Nl - ustart, c.stream);
-        if (r.pj == kcol)  // diagonal tile: packed LU from A00
-            launch_copy2d(r.A00, v, Frow + loff, Nl, v, v, c.stream);
-    };
-    // step-5 solve of columns [loff + c0, loff + c0 + w): in place in A01, or
-    // direct from the pivot rows in A11 (rows [fnp - v, fnp) after the push)
-    // into A01Rcv
-    auto solve_left = [&](RankState &r, int64_t c0, int64_t w) -> int {
-        if (w <= 0) return 0;
-        if (direct)
-            return trsm_left_direct(c, r, k,
-                                    r.A11 + i64(r.fnp - v) * Nl + loff + c0, Nl,
-                                    r.A01Rcv + c0, Nl, w);
-        return trsm_left_lower(c, r, r.A01 + c0, wA01, w);
-    };
-    // slice-first: what follows the slice on the solve stream (c.stream here)
-    auto solve_rest = [&](RankState &r) -> int {
-        const int64_t s0 = lnext - loff;
-        if (sliced) {
-            // the columns the (b) pieces and later steps read
-            const int64_t wrest = Nl - (lnext + v);
-            if (wrest > 0 &&
-                push_rows(r, r.A11, Nl, lnext + v, wrest, r.fnp - v, v,
-                          n_early0))
-                return CONFLUX_LU_EHIP;
-            if (wrest > 0 && !direct) {
-                launch_copy2d(r.A11 + i64(r.fnp - v) * Nl + lnext + v, Nl,
-                              r.A01pack + wfirst, wA01, v, wrest, c.stream);
-                launch_row_scatter(r.A01pack + wfirst, wA01, r.A01 + wfirst,
-                                   wA01, r.d_idx + 3 * v, v, wrest, c.stream);
-            }
-        }
-        if (dead < s0 && solve_left(r, dead, s0 - dead))
-            return CONFLUX_LU_EINTERNAL;
-        if (solve_left(r, s0 + v, wA01 - s0 - v)) return CONFLUX_LU_EINTERNAL;
-        store_u(r);
         return 0;
-    };
-    if (gap_on) {
-        g_gap.to_trsm += gap_ms(gap_t0, GapClock::now());
-        ++g_gap.steps;
     }
-    if (split_trsm) {
-        HIPCHK(hipEventRecord(c.ev_t3, c.stream));
-        HIPCHK(hipStreamWaitEvent(c.trsm_stream, c.ev_t3, 0));
-        hipStream_t saved = c.stream;
-        c.stream = c.trsm_stream;
-        for (auto &r : c.rs) {
-            if (r.pi != krow || r.pk != 0) continue;
-            if (!slice_first) {
-                if (solve_left(r, dead, wA01 - dead))
-                    return CONFLUX_LU_EINTERNAL;
-                store_u(r);
+    RankState &me = c.rs[0];
+    if (me.pk != 0) return 0;
+    NCCLCHK(ncclGroupStart());
+    if (me.pi != krow) {
+        const int cnt = (int)sp.lrows[me.pi].size();
+        if (cnt)
+            NCCLCHK(ncclSend(me.A01pack, i64(cnt) * wA01, ncclDouble,
+                             grank_of(c, krow, me.pj, 0), c.comm, c.stream));
+    } else {
+        int64_t off = 0;
+        for (int pi = 0; pi < Px; ++pi) {
+            if (pi == krow) continue;
+            const int cnt = (int)sp.lrows[pi].size();
+            if (cnt)
+                NCCLCHK(ncclRecv(me.redtmp + off, i64(cnt) * wA01, ncclDouble,
+                                 grank_of(c, pi, me.pj, 0), c.comm, c.stream));
+            off += i64(cnt) * wA01;
+        }
+    }
+    NCCLCHK(ncclGroupEnd());
+    if (me.pi != krow) return 0;
+    // scatter own + received rows into A01 by pivot order
+    const int cnt_own = (int)sp.lrows[krow].size();
+    if (cnt_own) {
+        HIPCHK(hipMemcpyAsync(me.d_idx + 3 * v, sp.order[krow].data(),
+                              cnt_own * 4, hipMemcpyHostToDevice, c.stream));
+        launch_row_scatter(me.A01pack, wA01, me.A01, wA01, me.d_idx + 3 * v,
+                           cnt_own, st.wfirst, c.stream);
+    }
+    int64_t off = 0;
+    for (int pi = 0; pi < Px; ++pi) {
+        if (pi == krow) continue;
+        const int cnt = (int)sp.lrows[pi].size();
+        if (cnt) {
+            HIPCHK(hipMemcpyAsync(me.d_idx, sp.order[pi].data(), cnt * 4,
+                                  hipMemcpyHostToDevice, c.stream));
+            launch_row_scatter(me.redtmp + off, wA01, me.A01, wA01, me.d_idx,
+                               cnt, wA01, c.stream);
+        }
+        off += i64(cnt) * wA01;
+    }
+    return 0;
+}
+
+// store_factors: ship this step's pivot rows' L history to row krow (C10).
+// Source: hist rows fnp-cnt..fnp (post-push); destination: Fres rows
+// ltik*v + order[i].
+int ship_history(Ctx &c, const Step &st, StepPlan &sp) {
+    if (!c.store_factors || st.k == 0) return 0;
+    const int v = c.v, k = st.k, krow = st.krow;
+    const int64_t Nl = c.Nl;
+    const int ltik = k / c.Px;  // local row-tile of global tile k on row krow
+    for (int pj = 0; pj < c.Py; ++pj) {
+        const int64_t histcols =
+            i64(v) * (pj < st.kcol ? k / c.Py + 1 : k / c.Py);
+        if (histcols == 0) continue;
+        for (int pi = 0; pi < c.Px; ++pi) {
+            const int cnt = (int)sp.lrows[pi].size();
+            if (!cnt) continue;
+            RankState *src = get_rs(c, pi, pj, 0);
+            RankState *dst = get_rs(c, krow, pj, 0);
+            if (c.sim) {
+                HIPCHK(hipMemcpyAsync(dst->d_idx + 2 * v, sp.order[pi].data(),
+                                      cnt * 4, hipMemcpyHostToDevice,
+                                      c.stream));
+                launch_row_scatter(src->A10hist + i64(src->fnp - cnt) * Nl, Nl,
+                                   dst->Fres + i64(ltik) * v * Nl, Nl,
+                                   dst->d_idx + 2 * v, cnt, histcols,
+                                   c.stream);
                 continue;
             }
-            const int64_t s0 = lnext - loff;  // slice start in A01
-            if (solve_left(r, s0, v)) return CONFLUX_LU_EINTERNAL;
-            HIPCHK(hipEventRecord(c.ev_t5a, c.stream));
-            // sliced: the rest is enqueued behind the (a) GEMM below.
-            // Started here, its 32-column blocks (one per CU, the whole LDS)
-            // take the CUs from under (a), which is on the critical path and
-            // then runs 2.5x as long (profiles/r08_gap_after.csv)
-            if (!sliced)
-                if (int rc = solve_rest(r)) return rc;
+            RankState &me = c.rs[0];
+            if (src && dst) {
+                // (sliced: the second part of the A11 push still needs the
+                // late list at d_idx + 2v; the order list of this one rank
+                // row is already at d_idx + 3v)
+                int *const d_ord = me.d_idx + (st.sliced ? 3 : 2) * v;
+                if (!st.sliced)
+                    HIPCHK(hipMemcpyAsync(d_ord, sp.order[pi].data(), cnt * 4,
+                                          hipMemcpyHostToDevice, c.stream));
+                launch_row_scatter(me.A10hist + i64(me.fnp - cnt) * Nl, Nl,
+                                   me.Fres + i64(ltik) * v * Nl, Nl, d_ord,
+                                   cnt, histcols, c.stream);
+            } else if (src) {
+                launch_copy2d(me.A10hist + i64(me.fnp - cnt) * Nl, Nl,
+                              me.rowtmp, histcols, cnt, histcols, c.stream);
+                NCCLCHK(ncclSend(me.rowtmp, i64(cnt) * histcols, ncclDouble,
+                                 grank_of(c, krow, pj, 0), c.comm, c.stream));
+            } else if (dst) {
+                NCCLCHK(ncclRecv(me.rowtmp, i64(cnt) * histcols, ncclDouble,
+                                 grank_of(c, pi, pj, 0), c.comm, c.stream));
+                HIPCHK(hipMemcpyAsync(me.d_idx + 2 * v, sp.order[pi].data(),
+                                      cnt * 4, hipMemcpyHostToDevice,
+                                      c.stream));
+                launch_row_scatter(me.rowtmp, histcols,
+                                   me.Fres + i64(ltik) * v * Nl, Nl,
+                                   me.d_idx + 2 * v, cnt, histcols, c.stream);
+            }
         }
-        if (!sliced) HIPCHK(hipEventRecord(c.ev_t5, c.stream));
-        c.stream = saved;
     }
+    return 0;
+}
 
-    for (auto &r : c.rs)
-        nanscan(c, "A11.postpush", k, r.A11, i64(c.Ml) * Nl);
-    // ---- step 4: A10 <- A10 U^-1, slab-split, spread (C8) ------------------
+// store_factors: the solved U rows (and the diagonal tile) go to Fres, on
+// whichever stream the solve ran
+void store_u(Ctx &c, const Step &st, RankState &r) {
+    if (!c.store_factors) return;
+    const int v = c.v, k = st.k;
+    const int64_t Nl = c.Nl;
+    double *Frow = r.Fres + i64(k / c.Px) * v * Nl;  // local row tile of k
+    // U region starts at this rank's first local column tile with global
+    // tile >= k; columns left of it carry stale already-factored data the
+    // reference never reads (cf. oracle lu_oracle.py step-5 `gcs >= off`
+    // mask)
+    // (dead: the diagonal tile's columns were not solved for; A00 below)
+    const int64_t ustart =
+        i64(v) * (r.pj < st.kcol ? k / c.Py + 1 : k / c.Py) + st.dead;
+    if (Nl - ustart > 0 && st.direct)
+        launch_copy2d(r.A01Rcv + (ustart - st.loff), Nl, Frow + ustart, Nl, v,
+                      Nl - ustart, c.stream);
+    else if (Nl - ustart > 0)
+        launch_copy2d(r.A01 + (ustart - st.loff), st.wA01, Frow + ustart, Nl,
+                      v, Nl - ustart, c.stream);
+    if (r.pj == st.kcol)  // diagonal tile: packed LU from A00
+        launch_copy2d(r.A00, v, Frow + st.loff, Nl, v, v, c.stream);
+}
+
+// step-5 solve of columns [loff + c0, loff + c0 + w): in place in A01, or
+// direct from the pivot rows in A11 (rows [fnp - v, fnp) after the push)
+// into A01Rcv
+int solve_left(Ctx &c, const Step &st, RankState &r, int64_t c0, int64_t w) {
+    if (w <= 0) return 0;
+    if (st.direct)
+        return trsm_left_direct(
+            c, r, st.k, r.A11 + i64(r.fnp - c.v) * c.Nl + st.loff + c0, c.Nl,
+            r.A01Rcv + c0, c.Nl, w);
+    return trsm_left_lower(c, r, r.A01 + c0, st.wA01, w);
+}
+
+// slice-first: what follows the slice on the solve stream (c.stream here)
+int solve_rest(Ctx &c, const Step &st, const StepPlan &sp, RankState &r) {
+    const int v = c.v;
+    const int64_t Nl = c.Nl, s0 = st.lnext - st.loff;
+    if (st.sliced) {
+        // the columns the (b) pieces and later steps read
+        const int64_t wrest = Nl - (st.lnext + v);
+        if (wrest > 0 && push_rows(c, r, r.A11, Nl, st.lnext + v, wrest,
+                                   r.fnp - v, v, sp.n_early0))
+            return CONFLUX_LU_EHIP;
+        if (wrest > 0 && !st.direct) {
+            launch_copy2d(r.A11 + i64(r.fnp - v) * Nl + st.lnext + v, Nl,
+                          r.A01pack + st.wfirst, st.wA01, v, wrest, c.stream);
+            launch_row_scatter(r.A01pack + st.wfirst, st.wA01,
+                               r.A01 + st.wfirst, st.wA01, r.d_idx + 3 * v, v,
+                               wrest, c.stream);
+        }
+    }
+    if (st.dead < s0 && solve_left(c, st, r, st.dead, s0 - st.dead))
+        return CONFLUX_LU_EINTERNAL;
+    if (solve_left(c, st, r, s0 + v, st.wA01 - s0 - v))
+        return CONFLUX_LU_EINTERNAL;
+    store_u(c, st, r);
+    return 0;
+}
+
+// Steps 4 & 5 compute: the two panel TRSMs are independent after step 3, so
+// with split_trsm the step-5 TRSM is issued here on the solve stream and runs
+// concurrently with the step-4 TRSM (the spreads stay ordered on the main
+// stream, C8 overlapping the step-5 solve like the reference's Iscatterv
+// window, conflux_opt.hpp:1424-1615).
+int start_left_solve(Ctx &c, const Step &st, const StepPlan &sp) {
+    if (!st.split_trsm) return 0;
+    HIPCHK(hipEventRecord(c.ev_t3, c.stream));
+    HIPCHK(hipStreamWaitEvent(c.trsm_stream, c.ev_t3, 0));
+    StreamGuard on_solve_stream(c, c.trsm_stream);
     for (auto &r : c.rs) {
-        if (r.pj != kcol || r.pk != 0) continue;
-        if (direct) {
+        if (r.pi != st.krow || r.pk != 0) continue;
+        if (!st.slice_first) {
+            if (solve_left(c, st, r, st.dead, st.wA01 - st.dead))
+                return CONFLUX_LU_EINTERNAL;
+            store_u(c, st, r);
+            continue;
+        }
+        // the slice starts at lnext - loff in A01
+        if (solve_left(c, st, r, st.lnext - st.loff, c.v))
+            return CONFLUX_LU_EINTERNAL;
+        HIPCHK(hipEventRecord(c.ev_t5a, c.stream));
+        // sliced: the rest is enqueued behind the (a) GEMM
+        // (finish_left_solve).  Started here, its 32-column blocks (one per
+        // CU, the whole LDS) take the CUs from under (a), which is on the
+        // critical path and then runs 2.5x as long
+        // (profiles/r08_gap_after.csv)
+        if (!st.sliced)
+            if (int rc = solve_rest(c, st, sp, r)) return rc;
+    }
+    if (!st.sliced) HIPCHK(hipEventRecord(c.ev_t5, c.stream));
+    return 0;
+}
+
+// step 4: A10 <- A10 U^-1, slab-split, spread (C8)
+int right_solve_and_spread(Ctx &c, const Step &st) {
+    const int v = c.v, k = st.k;
+    const int64_t Nl = c.Nl;
+    for (auto &r : c.rs) {
+        if (r.pj != st.kcol || r.pk != 0) continue;
+        if (st.direct) {
             // source: the panel's column block of A11 below the pivot rows
             // (what the pushed A10 holds on the staged path), untouched;
             // destination: the GEMM operand itself, no slab spread
             nanscan(c, "A00", k, r.A00, i64(v) * v);
             if (r.nact > 0 &&
-                trsm_right_direct(c, r, k, r.A11 + i64(r.fnp) * Nl + loff, Nl,
-                                  r.A10Rcv, c.nlayr, r.nact))
+                trsm_right_direct(c, r, k, r.A11 + i64(r.fnp) * Nl + st.loff,
+                                  Nl, r.A10Rcv, c.nlayr, r.nact))
                 return CONFLUX_LU_EINTERNAL;
             if (c.store_factors)
                 launch_copy2d(r.A10Rcv, c.nlayr,
-                              r.A10hist + i64(r.fnp) * Nl + loff, Nl, r.nact, v,
-                              c.stream);
+                              r.A10hist + i64(r.fnp) * Nl + st.loff, Nl,
+                              r.nact, v, c.stream);
             continue;
         }
         nanscan(c, "A10.pre", k, r.A10 + i64(r.fnp) * v, i64(r.nact) * v);
@@ -1591,181 +1556,216 @@ int run_step(Ctx &c, int k, StepPlan &sp) {
         nanscan(c, "A10.post", k, r.A10 + i64(r.fnp) * v, i64(r.nact) * v);
         if (c.store_factors)
             launch_copy2d(r.A10 + i64(r.fnp) * v, v,
-                          r.A10hist + i64(r.fnp) * Nl + loff, Nl, r.nact, v,
+                          r.A10hist + i64(r.fnp) * Nl + st.loff, Nl, r.nact, v,
                           c.stream);
     }
-    if (!direct)
-        if (int rc = spread_col_slabs(
-                c, kcol, [](const RankState &r) { return r.fnp; }))
-            return rc;
+    if (st.direct) return 0;
+    return spread_col_slabs(c, st.kcol,
+                            [](const RankState &r) { return r.fnp; });
+}
 
-    // ---- step 5: A01 <- L^-1 A01 (already issued on the second stream
-    // when split_trsm; the C9 spread below waits for it), spread (C9) -------
-    if (!split_trsm) {
+// step 5: A01 <- L^-1 A01 (already issued on the solve stream when
+// split_trsm; the C9 spread waits for it), spread (C9)
+int left_solve_and_spread(Ctx &c, const Step &st) {
+    const int64_t Nl = c.Nl, wA01 = st.wA01;
+    if (!st.split_trsm) {
         for (auto &r : c.rs) {
-            if (r.pi != krow || r.pk != 0) continue;
-            if (solve_left(r, dead, wA01 - dead)) return CONFLUX_LU_EINTERNAL;
-            store_u(r);
+            if (r.pi != st.krow || r.pk != 0) continue;
+            if (solve_left(c, st, r, st.dead, wA01 - st.dead))
+                return CONFLUX_LU_EINTERNAL;
+            store_u(c, st, r);
         }
-    } else if (!slice_first) {
+    } else if (!st.slice_first) {
         HIPCHK(hipStreamWaitEvent(c.stream, c.ev_t5, 0));
     }
-    if (Pz == 1 && Px == 1) {
-        RankState &r = c.rs[0];
-        if (c.sim)
-            for (auto &x : c.rs)
-                launch_copy2d(x.A01, wA01, x.A01Rcv, Nl, c.nlayr, wA01,
-                              c.stream);
-        else if (slice_first) {
-            // slice only; the rest is copied after ev_t5 below, before the
-            // (b) trailing pieces that read it
-            HIPCHK(hipStreamWaitEvent(c.stream, c.ev_t5a, 0));
-            const int64_t s0 = lnext - loff;
-            if (!direct)
-                launch_copy2d(r.A01 + s0, wA01, r.A01Rcv + s0, Nl, c.nlayr, v,
-                              c.stream);
-        } else if (!direct)
-            launch_copy2d(r.A01 + dead, wA01, r.A01Rcv + dead, Nl, c.nlayr,
-                          wA01 - dead, c.stream);
-    } else if (int rc = spread_row_panel(
-                   c, krow, [&](int) { return wA01; },
-                   [](int) { return int64_t(0); }))
-        return rc;
+    if (c.Pz != 1 || c.Px != 1)
+        return spread_row_panel(
+            c, st.krow, [wA01](int) { return wA01; },
+            [](int) { return int64_t(0); });
+    RankState &r = c.rs[0];
+    if (c.sim)
+        for (auto &x : c.rs)
+            launch_copy2d(x.A01, wA01, x.A01Rcv, Nl, c.nlayr, wA01, c.stream);
+    else if (st.slice_first) {
+        // slice only; the rest is copied after ev_t5 (finish_left_solve),
+        // before the (b) trailing pieces that read it
+        HIPCHK(hipStreamWaitEvent(c.stream, c.ev_t5a, 0));
+        const int64_t s0 = st.lnext - st.loff;
+        if (!st.direct)
+            launch_copy2d(r.A01 + s0, wA01, r.A01Rcv + s0, Nl, c.nlayr, c.v,
+                          c.stream);
+    } else if (!st.direct)
+        launch_copy2d(r.A01 + st.dead, wA01, r.A01Rcv + st.dead, Nl, c.nlayr,
+                      wA01 - st.dead, c.stream);
+    return 0;
+}
 
-    // ---- step 6: trailing update (the flop carrier), split for lookahead --
-    auto gemm_piece = [&](RankState &r, int64_t col0, int64_t ncols,
-                          int cap) -> int {
-        if (r.nact <= 0 || ncols <= 0) return 0;
-        const double fl = 2.0 * r.nact * (double)ncols * c.nlayr;
-        size_t slot;
-        if (ev_begin(c, 0, fl, &slot)) return CONFLUX_LU_EHIP;
-        launch_dgemm_f64(r.A10Rcv, c.nlayr, r.A01Rcv + (col0 - loff), Nl,
-                         r.A11 + i64(r.fnp) * Nl + col0, Nl, r.nact, ncols,
-                         c.nlayr, c.stream, cap);
-        return ev_end(c, slot) ? CONFLUX_LU_EHIP : 0;
-    };
-    const char *lk = getenv("CONFLUX_LOOKAHEAD");
-    bool async_look = look && !c.sim && c.panel_stream &&
-                      (lk ? atoi(lk) != 0 : true);
-    // While the panel of step k+1 runs concurrently, cap the trailing
-    // update's grid so whole CUs stay free for it: an uncapped GEMM flood
-    // starves the panel until the queue drains (measured 256 ms vs 251 ms
-    // sequential at N=16384 before this cap).  Panel blocks need 67 KB LDS
-    // (256x256 shape, 2 blocks/CU); the default cap leaves 40 of 256 CUs
-    // free = up to 80 co-resident panel blocks.
-    int gcap = 0;
-    if (async_look) {
-        static int env_cap = -1;
-        if (env_cap < 0) {
-            const char *e = getenv("CONFLUX_GEMM_CAP");
-            env_cap = e ? atoi(e) : 432;  // r02 re-sweep with 256-row panel
-                                          // blocks: 432 ~= 400 (201.5 ms)
-                                          // > 448 > 464 at N=16384
-        }
-        // Only ranks that RUN step k+1's panel factor need the cap (and
-        // the residency guard): pj == ncol AND pk == 0 (the factor runs on
-        // layer 0 only — conflux_opt.hpp:689).  Other ranks overlap only
-        // the panel chain's comm and keep the full-width GEMM (r02 fix:
-        // pk > 0 ranks on 1x1xPz grids were capping for a factor they
-        // never run).
-        int panel_rows = 0;
-        for (auto &r : c.rs)
-            if (r.pj == ncol && r.pk == 0)
-                panel_rows = std::max(panel_rows, r.nact);
-        if (panel_rows > 0) {
-            gcap = env_cap;
-            // Residency guard: the persistent capped GEMM holds its CUs
-            // for the whole update, so if step k+1's panel needs more
-            // co-resident blocks than the cap leaves free (tall panels at
-            // N >= 32768), the overlap would serialize anyway — keep the
-            // sequential order and the full-width GEMM instead.
-            const int nblocks = (panel_rows + conflux_panel_rpb() - 1) /
-                                conflux_panel_rpb();
-            const int bpc = conflux_panel_blocks_per_cu();
-            const int free_cus = 256 - (gcap + 1) / 2;
-            if ((nblocks + bpc - 1) / bpc > free_cus) {
-                async_look = false;
-                gcap = 0;
-            }
-        }
+// slice-first: the rest of the A01 solve feeds the (b) pieces
+int finish_left_solve(Ctx &c, const Step &st, const StepPlan &sp) {
+    if (!st.slice_first) return 0;
+    RankState &r = c.rs[0];
+    if (st.sliced) {
+        HIPCHK(hipStreamWaitEvent(c.trsm_stream, c.ev_pc, 0));
+        StreamGuard on_solve_stream(c, c.trsm_stream);
+        if (int rc = solve_rest(c, st, sp, r)) return rc;
+        HIPCHK(hipEventRecord(c.ev_t5, c.stream));
     }
+    HIPCHK(hipStreamWaitEvent(c.stream, c.ev_t5, 0));
+    const int64_t s0 = st.lnext - st.loff, wA01 = st.wA01;
+    if (!st.direct && s0 > st.dead)
+        launch_copy2d(r.A01 + st.dead, wA01, r.A01Rcv + st.dead, c.Nl, c.nlayr,
+                      s0 - st.dead, c.stream);
+    if (!st.direct && wA01 - s0 - c.v > 0)
+        launch_copy2d(r.A01 + s0 + c.v, wA01, r.A01Rcv + s0 + c.v, c.Nl,
+                      c.nlayr, wA01 - s0 - c.v, c.stream);
+    return 0;
+}
+
+// one piece of the trailing update: columns [col0, col0 + ncols) of the
+// active rows, on a grid of at most `cap` workgroups (0 = uncapped)
+int gemm_piece(Ctx &c, const Step &st, RankState &r, int64_t col0,
+               int64_t ncols, int cap) {
+    if (r.nact <= 0 || ncols <= 0) return 0;
+    const double fl = 2.0 * r.nact * (double)ncols * c.nlayr;
+    size_t slot;
+    if (ev_begin(c, 0, fl, &slot)) return CONFLUX_LU_EHIP;
+    launch_dgemm_f64(r.A10Rcv, c.nlayr, r.A01Rcv + (col0 - st.loff), c.Nl,
+                     r.A11 + i64(r.fnp) * c.Nl + col0, c.Nl, r.nact, ncols,
+                     c.nlayr, c.stream, cap);
+    return ev_end(c, slot) ? CONFLUX_LU_EHIP : 0;
+}
+
+// The look-ahead decision of a step, made here and nowhere else (after the
+// push: it reads nact).  async = step k+1's panel chain runs on the panel
+// stream concurrently with the (b) pieces; gcap = the grid cap of those
+// pieces (0 = uncapped).
+//
+// While the panel of step k+1 runs concurrently, the trailing update's grid
+// is capped so whole CUs stay free for it: an uncapped GEMM flood starves
+// the panel until the queue drains (measured 256 ms vs 251 ms sequential at
+// N=16384 before this cap).  Panel blocks need 67 KB LDS (256x256 shape, 2
+// blocks/CU); the default cap leaves 40 of 256 CUs free = up to 80
+// co-resident panel blocks.
+//
+// INVARIANT: st.slice_first is decided before the push from the same knob
+// and stays on when the residency guard below turns async off.  That is
+// legal: ev_pc is recorded whenever a panel stream exists, so the sliced
+// rest and the slice's waits have their events either way; the step merely
+// pays the slice's 7 ms without a concurrent panel to gain from it.
+struct LookAhead {
+    bool async = false;
+    int gcap = 0;
+};
+LookAhead plan_lookahead(const Ctx &c, const Step &st) {
+    LookAhead la;
+    if (!(st.look && !c.sim && c.panel_stream && c.knobs.lookahead)) return la;
+    la.async = true;
+    // Only ranks that RUN step k+1's panel factor need the cap (and the
+    // residency guard): pj == ncol AND pk == 0 (the factor runs on layer 0
+    // only — conflux_opt.hpp:689).  Other ranks overlap only the panel
+    // chain's comm and keep the full-width GEMM (r02 fix: pk > 0 ranks on
+    // 1x1xPz grids were capping for a factor they never run).
+    int panel_rows = 0;
+    for (const auto &r : c.rs)
+        if (r.pj == st.ncol && r.pk == 0)
+            panel_rows = std::max(panel_rows, r.nact);
+    if (panel_rows <= 0) return la;
+    la.gcap = c.knobs.gemm_cap;
+    // Residency guard: the persistent capped GEMM holds its CUs for the
+    // whole update, so if step k+1's panel needs more co-resident blocks
+    // than the cap leaves free (tall panels at N >= 32768), the overlap
+    // would serialize anyway — keep the sequential order and the full-width
+    // GEMM instead.
+    const int nblocks =
+        (panel_rows + conflux_panel_rpb() - 1) / conflux_panel_rpb();
+    const int bpc = conflux_panel_blocks_per_cu();
+    const int free_cus = 256 - (la.gcap + 1) / 2;
+    if ((nblocks + bpc - 1) / bpc > free_cus) la = LookAhead{};
+    return la;
+}
+
+// step 6: trailing update (the flop carrier), split for the look-ahead: (a)
+// the columns of step k+1's panel FIRST, (b) the rest, (c) phase01(k+1) on
+// the panel stream CONCURRENTLY with (b).  Numerically identical: the column
+// split does not reorder any K-sum.  On exit sp holds step k+1's plan.
+int trailing_update(Ctx &c, const Step &st, StepPlan &sp) {
+    const int v = c.v, k = st.k;
+    const int64_t Nl = c.Nl;
+    const LookAhead la = plan_lookahead(c, st);
     for (auto &r : c.rs) {
         nanscan(c, "A10Rcv", k, r.A10Rcv, i64(r.nact) * c.nlayr);
-        nanscan(c, "A01Rcv", k, r.A01Rcv, i64(c.nlayr - 1) * Nl + (Nl - loff));
+        nanscan(c, "A01Rcv", k, r.A01Rcv,
+                i64(c.nlayr - 1) * Nl + (Nl - st.loff));
     }
     // (a) the columns step k+1's panel needs, first
-    if (look)
+    if (st.look)
         for (auto &r : c.rs)
-            if (r.pj == ncol)
-                if (gemm_piece(r, lnext, v, 0)) return CONFLUX_LU_EHIP;
-    if (look)
+            if (r.pj == st.ncol)
+                if (gemm_piece(c, st, r, st.lnext, v, 0))
+                    return CONFLUX_LU_EHIP;
+    if (st.look)
         for (auto &r : c.rs)
-            if (r.pj == ncol)
+            if (r.pj == st.ncol)
                 nanscan(c, "A11.a-cols", k,
-                        r.A11 + i64(r.fnp) * Nl + lnext, i64(r.nact) * Nl);
-    if (look && !c.sim && c.panel_stream) {
+                        r.A11 + i64(r.fnp) * Nl + st.lnext, i64(r.nact) * Nl);
+    if (st.look && !c.sim && c.panel_stream) {
         HIPCHK(hipEventRecord(c.ev_pc, c.stream));
-        if (gap_on) {
-            g_gap.to_evpc += gap_ms(gap_t0, GapClock::now());
+        if (c.knobs.gap_stats) {
+            g_gap.to_evpc += gap_ms(g_gap.t0, GapClock::now());
             ++g_gap.evpc_steps;
         }
     }
-    if (slice_first) {
-        // rest of the A01 solve feeds the (b) pieces below
-        RankState &r = c.rs[0];
-        if (sliced) {
-            hipStream_t saved = c.stream;
-            HIPCHK(hipStreamWaitEvent(c.trsm_stream, c.ev_pc, 0));
-            c.stream = c.trsm_stream;
-            const int rc = solve_rest(r);
-            if (!rc) HIPCHK(hipEventRecord(c.ev_t5, c.stream));
-            c.stream = saved;
-            if (rc) return rc;
-        }
-        HIPCHK(hipStreamWaitEvent(c.stream, c.ev_t5, 0));
-        const int64_t s0 = lnext - loff;
-        if (!direct && s0 > dead)
-            launch_copy2d(r.A01 + dead, wA01, r.A01Rcv + dead, Nl, c.nlayr,
-                          s0 - dead, c.stream);
-        if (!direct && wA01 - s0 - v > 0)
-            launch_copy2d(r.A01 + s0 + v, wA01, r.A01Rcv + s0 + v, Nl,
-                          c.nlayr, wA01 - s0 - v, c.stream);
-    }
+    if (int rc = finish_left_solve(c, st, sp)) return rc;
     // (b) the rest of the trailing update — capped while the panel runs.
     // It must be ENQUEUED before phase01: phase01 ends in a host sync (the
     // pivot D2H), so anything enqueued after it cannot overlap the panel.
     for (auto &r : c.rs) {
-        if (look && r.pj == ncol) {
+        if (st.look && r.pj == st.ncol) {
             // (dead: with Py = 1 this first piece is the column block of
             // the panel just factored, which no later step reads)
-            if (gemm_piece(r, loff + dead, lnext - loff - dead, gcap))
+            if (gemm_piece(c, st, r, st.loff + st.dead,
+                           st.lnext - st.loff - st.dead, la.gcap))
                 return CONFLUX_LU_EHIP;
-            if (gemm_piece(r, lnext + v, Nl - (lnext + v), gcap))
+            if (gemm_piece(c, st, r, st.lnext + v, Nl - (st.lnext + v),
+                           la.gcap))
                 return CONFLUX_LU_EHIP;
         } else {
-            if (gemm_piece(r, loff + dead, wA01 - dead, gcap))
+            if (gemm_piece(c, st, r, st.loff + st.dead, st.wA01 - st.dead,
+                           la.gcap))
                 return CONFLUX_LU_EHIP;
         }
     }
     // (c) lookahead: step k+1's panel chain on the panel stream, gated on
     // ev_pc (= its columns updated), running concurrently with (b) on the
-    // CUs the cap left free.  Numerically identical: the column split does
-    // not reorder any K-sum.
-    if (look) {
-        hipStream_t saved = c.stream;
-        if (async_look) {
-            HIPCHK(hipStreamWaitEvent(c.panel_stream, c.ev_pc, 0));
-            c.stream = c.panel_stream;
-        }
-        StepPlan nsp;
-        int rc = phase01(c, k + 1, nsp);
-        c.stream = saved;
-        if (rc) return rc;
-        sp = std::move(nsp);
-    }
+    // CUs the cap left free
+    if (!st.look) return 0;
+    if (la.async) HIPCHK(hipStreamWaitEvent(c.panel_stream, c.ev_pc, 0));
+    StreamGuard on_panel_stream(c, la.async ? c.panel_stream : c.stream);
+    StepPlan nsp;
+    if (int rc = phase01(c, k + 1, nsp)) return rc;
+    sp = std::move(nsp);
     return 0;
 }
 
+// Steps 2..6 of superstep k; sp holds this step's pivot
+// plan (from phase01) and, on exit, step k+1's.
+int run_step(Ctx &c, int k, StepPlan &sp) {
+    const Step st = make_step(c, k);
+    if (c.knobs.gap_stats) g_gap.t0 = GapClock::now();
+    if (int rc = push_pivot_rows(c, st, sp)) return rc;       // 2, C7
+    if (int rc = route_pivot_rows(c, st, sp)) return rc;      // 3, C5/C6
+    if (int rc = ship_history(c, st, sp)) return rc;          // C10
+    if (c.knobs.gap_stats) {
+        g_gap.to_trsm += gap_ms(g_gap.t0, GapClock::now());
+        ++g_gap.steps;
+    }
+    if (int rc = start_left_solve(c, st, sp)) return rc;      // 5, split
+    for (auto &r : c.rs)
+        nanscan(c, "A11.postpush", k, r.A11, i64(c.Ml) * c.Nl);
+    if (int rc = right_solve_and_spread(c, st)) return rc;    // 4, C8
+    if (int rc = left_solve_and_spread(c, st)) return rc;     // 5, C9
+    return trailing_update(c, st, sp);                        // 6, 0/1 of k+1
+}
 
 // ===========================================================================
 // Cholesky (CONFCHOX path — SURVEY §8f1, reference src/conflux/cholesky/):
@@ -1963,11 +1963,7 @@ int chol_step(Ctx &c, int k) {
     // the (Nl x nlayr) B^T operand.  Tiles with global row tile < col tile
     // are never read anywhere (only the lower triangle is meaningful), so
     // masked-out regions are simply untouched.
-    static int rect_env = -1;
-    if (rect_env < 0) {
-        const char *e = getenv("CONFLUX_CHOL_RECT");
-        rect_env = e ? atoi(e) : 1;
-    }
+    static const int rect_env = env_int("CONFLUX_CHOL_RECT", 1);
     for (auto &r : c.rs) {
         const int f2 = f2_of(r.pi);
         const int ltj0 = (r.pj <= k) ? (k - r.pj) / Py + 1 : 0;
@@ -2085,11 +2081,7 @@ int chol_c4_1r(Ctx &c, int k, double *rcvA, double *rcvB, bool slice_only,
     double fl = 0;
     for (int j = k + 2; j < Nt; ++j) fl += 2.0 * (c.Ml - i64(j) * v) * v * c.nlayr;
     const bool use_rect = v % 128 == 0 && i64(M2r) * 4 / 128 <= 512;
-    static int dbg = -1;
-    if (dbg < 0) {
-        const char *e = getenv("CONFLUX_CHOL_DEBUG");
-        dbg = e ? atoi(e) : 0;
-    }
+    static const int dbg = env_int("CONFLUX_CHOL_DEBUG", 0);
     if (dbg)
         std::fprintf(stderr, "[c4_1r] k=%d M2r=%d rect=%d\n", k, M2r,
                      (int)use_rect);
@@ -2116,11 +2108,7 @@ int chol_c4_1r(Ctx &c, int k, double *rcvA, double *rcvB, bool slice_only,
 
 // every step of one Cholesky factorization (the timed body of chol_loop)
 int chol_steps(Ctx &c) {
-    static int chol_look = -1;
-    if (chol_look < 0) {
-        const char *e = getenv("CONFLUX_CHOL_LOOK");
-        chol_look = e ? atoi(e) : 1;
-    }
+    static const int chol_look = env_int("CONFLUX_CHOL_LOOK", 1);
     if (chol_look && !c.sim && c.world == 1 && c.Px == 1 && c.Py == 1 &&
         c.Pz == 1 && c.panel_stream) {
         RankState &r = c.rs[0];
@@ -2138,13 +2126,12 @@ int chol_steps(Ctx &c) {
                 return rc;
             HIPCHK(hipEventRecord(c.ev_pc, c.stream));
             HIPCHK(hipStreamWaitEvent(c.panel_stream, c.ev_pc, 0));
-            hipStream_t saved = c.stream;
-            c.stream = c.panel_stream;
-            rc = chol_chain_1r(c, k + 1, As2[par ^ 1], Bs2[par ^ 1]);
-            if (!rc && hipEventRecord(c.ev_t5, c.stream) != hipSuccess)
-                rc = CONFLUX_LU_EHIP;
-            c.stream = saved;
-            if (rc) return rc;
+            {
+                StreamGuard on_panel_stream(c, c.panel_stream);
+                if ((rc = chol_chain_1r(c, k + 1, As2[par ^ 1], Bs2[par ^ 1])))
+                    return rc;
+                HIPCHK(hipEventRecord(c.ev_t5, c.stream));
+            }
             if ((rc = chol_c4_1r(c, k, As2[par], Bs2[par], false, true)))
                 return rc;
             HIPCHK(hipStreamWaitEvent(c.stream, c.ev_t5, 0));
@@ -2415,8 +2402,7 @@ int conflux_lu_create(int N, int v, int Px, int Py, int Pz, int rank,
         if (alloc_rank(*c, c->rs[0], pi, pj, pk)) { delete c; return CONFLUX_LU_EHIP; }
         // panel-stream hardware queue priority: measured a wash at
         // N=16384 (205.3 vs 204.5 ms/step) — env-gated, default off
-        const char *pp = getenv("CONFLUX_PANEL_PRIO");
-        int prio_on = pp ? atoi(pp) : 0;
+        const int prio_on = env_int("CONFLUX_PANEL_PRIO", 0);
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
         if ((prio_on
@@ -2811,11 +2797,7 @@ int conflux_chol_validate(conflux_lu_ctx *c, double *resid) {
  * Real distributed runs (world > 1 processes) are NOT YET SUPPORTED: EARG on
  * every rank before any communication (a collective solve is a follow-up). */
 static bool solve_use_skinny() {  // env CONFLUX_SOLVE_SKINNY=0|1, read once
-    static int on = -1;
-    if (on < 0) {
-        const char *e = getenv("CONFLUX_SOLVE_SKINNY");
-        on = e ? (atoi(e) != 0) : 1;
-    }
+    static const int on = env_int("CONFLUX_SOLVE_SKINNY", 1);
     return on != 0;
 }
 
@@ -2828,11 +2810,7 @@ static bool solve_use_skinny() {  // env CONFLUX_SOLVE_SKINNY=0|1, read once
 // divides a larger v, else v.  env CONFLUX_SOLVE_BLOCK (read once) overrides
 // when it divides v.
 static int solve_block(int v) {
-    static int want = -1;
-    if (want < 0) {
-        const char *e = getenv("CONFLUX_SOLVE_BLOCK");
-        want = e ? atoi(e) : 0;
-    }
+    static const int want = env_int("CONFLUX_SOLVE_BLOCK", 0);
     if (want > 0 && want <= v && v % want == 0) return want;
     return (v > 128 && v % 128 == 0) ? 128 : v;
 }

@@ -251,6 +251,47 @@ def test_sequential_mode_bitwise(eng, monkeypatch):
     assert_same(r0, r2, f"N={N} v={v} random mode 0, sequential")
 
 
+_GUARD_CHILD = """
+import sys
+sys.path[:0] = [sys.argv[1], sys.argv[2]]
+import numpy as np
+import conflux_amd
+from test_one_rank_direct_gpu import ALL, factor_one_rank
+out = {}
+for mode in (ALL, 0):
+    perm, F = factor_one_rank(conflux_amd, mode, 1024, 128, "random")
+    out["perm%d" % mode], out["F%d" % mode] = perm, F
+np.savez(sys.argv[3], **out)
+"""
+
+
+def test_residency_guard_bitwise(eng, tmp_path):
+    """The look-ahead's residency guard: with CONFLUX_GEMM_CAP=510 (read once
+    per process, hence the fresh child) the capped update leaves one CU free.
+    At N = 1024, v = 128 the next panel has 896, 768, 640, 512, ... rows: 4,
+    3, 3 blocks of 256 rows at two per CU need two CUs, so the guard turns
+    the look-ahead off at steps 0 to 2 while the slice-first solve stays on;
+    from step 3 on the panel fits and runs concurrently under the cap.  Same
+    pivots and factors as this process's default-cap runs, in both modes."""
+    import os
+    import subprocess
+    import sys
+    N, v = 1024, 128
+    here = os.path.dirname(os.path.abspath(__file__))
+    out = str(tmp_path / "guard.npz")
+    env = dict(os.environ, CONFLUX_GEMM_CAP="510")
+    subprocess.run([sys.executable, "-c", _GUARD_CHILD,
+                    os.path.join(here, ".."), here, out],
+                   env=env, check=True, timeout=120)
+    got = np.load(out)
+    r0 = reference(eng, N, v, "random")
+    r7 = factor_one_rank(eng, ALL, N, v, "random")
+    for mode, mine in ((ALL, r7), (0, r0)):
+        child = (got[f"perm{mode}"], got[f"F{mode}"])
+        assert_same(mine, child, f"N={N} v={v} cap 510 mode {mode}")
+        assert_same(r0, child, f"N={N} v={v} cap 510 mode {mode} vs mode 0")
+
+
 def test_against_oracle(eng):
     N, v = 1024, 128
     A = matrix("random", N)
