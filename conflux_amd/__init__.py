@@ -132,6 +132,16 @@ def _load():
     lib.conflux_lu_debug_potrf_tile.argtypes = [i32, i64, i64, ptr]
     lib.conflux_lu_debug_poke_factor.argtypes = [ptr, i64, i64,
                                                  ctypes.c_double]
+    # device-resident dense interface (ptr arguments are device addresses)
+    dbl_p = ctypes.POINTER(ctypes.c_double)
+    lib.conflux_lu_set_matrix_device.argtypes = [ptr, ptr, i64, i32, i32]
+    lib.conflux_lu_get_factors_device.argtypes = [ptr, ptr, i64, ptr]
+    lib.conflux_lu_solve_device.argtypes = [ptr, ptr, i64, i32, i32, dbl_p]
+    lib.conflux_chol_solve_device.argtypes = [ptr, ptr, i64, i32, dbl_p]
+    lib.conflux_lu_slogdet.argtypes = [ptr, dbl_p, dbl_p]
+    lib.conflux_chol_logdet.argtypes = [ptr, dbl_p]
+    lib.conflux_lu_logical_order.argtypes = [ptr, ctypes.POINTER(i32)]
+    lib.conflux_lu_debug_get_input.argtypes = [ptr, i32, ptr]
     return lib
 
 
@@ -358,6 +368,69 @@ class Engine:
         return self._solve_refined(lib().conflux_chol_solve_refined,
                                    "solve_cholesky_refined", B, max_iter,
                                    return_info)
+
+    # ---- device-resident dense interface --------------------------------
+    # Pointers are raw device addresses (e.g. torch.Tensor.data_ptr()); the
+    # caller owns the buffers and must have finished producing them — the
+    # engine waits for its own stream only.  conflux_amd.dense wraps these
+    # for torch tensors.
+
+    @property
+    def n(self):
+        """Logical order of the current input: what set_matrix_device was
+        given, Npad after every other way of setting the matrix."""
+        n = ctypes.c_int()
+        _chk(lib().conflux_lu_logical_order(self._h, ctypes.byref(n)),
+             "logical_order")
+        return n.value
+
+    def set_matrix_device(self, dA, lda, n, order=0):
+        """Import the caller's dense n x n device matrix (order 0: element
+        (i, j) at dA[i*lda + j]; 1: dA[j*lda + i]) as blockdiag(A, I) of
+        order Npad; 1 <= n <= Npad.  Single process only."""
+        _chk(lib().conflux_lu_set_matrix_device(self._h, dA, lda, n, order),
+             "set_matrix_device")
+
+    def get_factors_device(self, dF, ldf, dperm):
+        """Leading n x n block of the stored factors into the row-major
+        device buffer dF (ldf >= n) and perm[:n] as int32 into dperm; either
+        may be None."""
+        _chk(lib().conflux_lu_get_factors_device(self._h, dF, ldf, dperm),
+             "get_factors_device")
+
+    def solve_device(self, dB, ldb, nrhs, trans=False):
+        """Solve A X = B (A^T X = B with trans) in place on the device buffer
+        dB (n x nrhs, row-major, ldb >= nrhs).  Returns the device time of
+        the two sweeps in ms."""
+        ms = ctypes.c_double()
+        _chk(lib().conflux_lu_solve_device(self._h, dB, ldb, nrhs,
+                                           int(bool(trans)),
+                                           ctypes.byref(ms)), "solve_device")
+        return ms.value
+
+    def solve_cholesky_device(self, dB, ldb, nrhs):
+        """solve_device for the factor of the last factor_cholesky()."""
+        ms = ctypes.c_double()
+        _chk(lib().conflux_chol_solve_device(self._h, dB, ldb, nrhs,
+                                             ctypes.byref(ms)),
+             "solve_cholesky_device")
+        return ms.value
+
+    def slogdet(self):
+        """(sign, log|det A|) of the n x n matrix of the last factor(), like
+        numpy.linalg.slogdet: (0.0, -inf) for a zero pivot."""
+        sg = ctypes.c_double()
+        ld = ctypes.c_double()
+        _chk(lib().conflux_lu_slogdet(self._h, ctypes.byref(sg),
+                                      ctypes.byref(ld)), "slogdet")
+        return sg.value, ld.value
+
+    def logdet_cholesky(self):
+        """log det A = 2 sum log L_ii of the last factor_cholesky()."""
+        ld = ctypes.c_double()
+        _chk(lib().conflux_chol_logdet(self._h, ctypes.byref(ld)),
+             "logdet_cholesky")
+        return ld.value
 
     def get_perm(self):
         import numpy as np

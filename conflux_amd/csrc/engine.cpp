@@ -134,6 +134,12 @@ struct Ctx {
     int N = 0, v = 0, Px = 1, Py = 1, Pz = 1;
     int M = 0, Ml = 0, Nl = 0, Nt = 0, Mt = 0, nlayr = 0, tA11x = 0, tA11y = 0;
     int world = 1, rank = 0;
+    int n = 0;                   // logical order of the current input: the
+                                 // leading n x n block is the caller's matrix,
+                                 // the rest identity padding
+                                 // (conflux_lu_set_matrix_device); N otherwise
+    int nf = 0;                  // the same for the matrix last snapshotted,
+                                 // i.e. the one the stored factors describe
     bool sim = false;            // all ranks in this process, 1 GPU
     bool input_dirty = true;     // A11 holds fresh input not yet snapshotted
     bool store_factors = true;
@@ -142,6 +148,8 @@ struct Ctx {
     double anorm_inf = -1;       // ||A11in||inf for the refined solves; < 0 =
                                  // not computed since the last factorization
     double anorm_one = -1;       // ||A11in||1 for the condition estimate, same
+    double anorm_lead[2] = {-1, -1};  // 1- and inf-norm of the leading nf x nf
+                                 // block when nf < N, same lifetime
     int pivoting = 1;            // 1 = tournament (reference), 0 = none
                                  // (EmptyPivot fast path)
     bool have_comm = false;
@@ -2376,6 +2384,7 @@ int conflux_lu_create(int N, int v, int Px, int Py, int Pz, int rank,
     c->rank = sim ? -1 : rank;
     c->sim = sim;
     c->M = N;
+    c->n = c->nf = N;
     c->Nt = N / v;
     c->Mt = N / v;
     c->tA11x = (c->Mt + Px - 1) / Px;
@@ -2445,6 +2454,7 @@ int conflux_lu_init_matrix(conflux_lu_ctx *c, uint64_t seed) {
     HIPCHK(hipGetLastError());  // a rejected launch is otherwise silent
     HIPCHK(hipStreamSynchronize(c->stream));
     c->input_dirty = true;
+    c->n = c->N;
     return CONFLUX_LU_OK;
 }
 
@@ -2456,6 +2466,7 @@ int conflux_lu_init_matrix_spd(conflux_lu_ctx *c, uint64_t seed) {
     HIPCHK(hipGetLastError());  // a rejected launch is otherwise silent
     HIPCHK(hipStreamSynchronize(c->stream));
     c->input_dirty = true;
+    c->n = c->N;
     return CONFLUX_LU_OK;
 }
 
@@ -2488,6 +2499,7 @@ int conflux_lu_set_matrix_local(conflux_lu_ctx *c, const double *local) {
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     c->input_dirty = true;
+    c->n = c->N;
     return CONFLUX_LU_OK;
 }
 
@@ -2505,6 +2517,7 @@ int conflux_lu_set_matrix_sim(conflux_lu_ctx *c, int grank,
                               hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->input_dirty = true;
+    c->n = c->N;
     return CONFLUX_LU_OK;
 }
 
@@ -2556,9 +2569,11 @@ static int snapshot_or_restore(conflux_lu_ctx *c) {
                                   hipMemcpyDeviceToDevice, c->stream));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->input_dirty) c->nf = c->n;
     c->input_dirty = false;
     c->anorm_inf = -1;
     c->anorm_one = -1;
+    c->anorm_lead[0] = c->anorm_lead[1] = -1;
     return CONFLUX_LU_OK;
 }
 
@@ -2967,10 +2982,18 @@ static void solve_sweeps(conflux_lu_ctx *c, bool chol, const SolveDev &sd,
 
 // trans (LU only): A^T X = B.  The sweeps run on B as uploaded and the
 // permutation comes last, as a scatter: P x = z, X[perm[r]] = Z[r].
+//
+// Two kinds of B share everything between staging and the sweeps.  Host
+// (ldb == 0): N_padded x nrhs, ld = nrhs, uploaded whole and downloaded whole.
+// Device (ldb >= nrhs): the caller's nf x nrhs window, ld = ldb, staged into
+// the same contiguous N x nrhs buffer with rows nf..N zero and cropped on the
+// way back; only the window's nf x nrhs doubles are written.
 static int solve_common(conflux_lu_ctx *c, bool chol, double *B, int nrhs,
-                        double *elapsed_ms, bool trans = false) {
+                        double *elapsed_ms, bool trans = false,
+                        int64_t ldb = 0) {
     if (int rc = solve_guard(c, chol, B, nrhs)) return rc;
     const int64_t N = c->N;
+    const bool dev = ldb > 0;
 
     SolveDev sd;
     double *Xd = nullptr, *Bd = nullptr;
@@ -2992,7 +3015,10 @@ static int solve_common(conflux_lu_ctx *c, bool chol, double *B, int nrhs,
         return rc;
     }
     SCHK(hipMalloc(&Xd, N * nrhs * 8));
-    if (chol || trans) {
+    if (dev) {
+        launch_rhs_stage_in(B, ldb, c->nf, (chol || trans) ? nullptr : sd.d_pm,
+                            Xd, N, nrhs, c->stream);
+    } else if (chol || trans) {
         SCHK(hipMemcpyAsync(Xd, B, N * nrhs * 8, hipMemcpyHostToDevice,
                             c->stream));
         if (trans) SCHK(hipMalloc(&Bd, N * nrhs * 8));
@@ -3001,7 +3027,8 @@ static int solve_common(conflux_lu_ctx *c, bool chol, double *B, int nrhs,
         SCHK(hipMemcpyAsync(Bd, B, N * nrhs * 8, hipMemcpyHostToDevice,
                             c->stream));
     }
-    if (!trans && solve_permute(c, chol, sd, chol ? Xd : Bd, Xd, nrhs)) {
+    if (!dev && !trans &&
+        solve_permute(c, chol, sd, chol ? Xd : Bd, Xd, nrhs)) {
         cleanup();
         return CONFLUX_LU_EHIP;
     }
@@ -3010,11 +3037,16 @@ static int solve_common(conflux_lu_ctx *c, bool chol, double *B, int nrhs,
     SCHK(hipEventRecord(e0, c->stream));
     solve_sweeps(c, chol, sd, Xd, nrhs, trans);
     SCHK(hipEventRecord(e1, c->stream));
-    if (trans)
-        launch_row_scatter(Xd, nrhs, Bd, nrhs, sd.d_pm, (int)N, nrhs,
-                           c->stream);
-    SCHK(hipMemcpyAsync(B, trans ? Bd : Xd, N * nrhs * 8,
-                        hipMemcpyDeviceToHost, c->stream));
+    if (dev) {
+        launch_rhs_stage_out(Xd, nrhs, c->nf, trans ? sd.d_pm : nullptr, B,
+                             ldb, c->stream);
+    } else {
+        if (trans)
+            launch_row_scatter(Xd, nrhs, Bd, nrhs, sd.d_pm, (int)N, nrhs,
+                               c->stream);
+        SCHK(hipMemcpyAsync(B, trans ? Bd : Xd, N * nrhs * 8,
+                            hipMemcpyDeviceToHost, c->stream));
+    }
     SCHK(hipStreamSynchronize(c->stream));
     SCHK(hipGetLastError());
     if (elapsed_ms) {
@@ -3045,6 +3077,170 @@ int conflux_lu_solve_trans(conflux_lu_ctx *c, double *B, int nrhs,
     return solve_common(c, false, B, nrhs, elapsed_ms, true);
 }
 
+/* The device-resident dense interface: the caller's n x n device matrix is
+ * embedded as blockdiag(A, I) in the padded order N.  All-zero candidate rows
+ * lose every tournament playoff and the leaf's zero-pivot rule never scales
+ * by them, so the padding stays an inert identity block: perm[n:] is the
+ * identity, F[n:, n:] == I, both off-diagonal blocks are zero, and the
+ * leading n rows of every solve answer the caller's own system.  Single
+ * process only (the one-rank engine and the simulation grids). */
+static bool dense_single_process(conflux_lu_ctx *c) {
+    return c && (c->sim || c->world == 1);
+}
+
+int conflux_lu_set_matrix_device(conflux_lu_ctx *c, const double *dA,
+                                 int64_t lda, int n, int order) {
+    if (!dense_single_process(c) || !dA || n < 1 || n > c->N || lda < n ||
+        (order != 0 && order != 1))
+        return CONFLUX_LU_EARG;
+    for (auto &r : c->rs) {
+        if (r.pk != 0)
+            launch_zero2d(r.A11, c->Nl, c->Ml, c->Nl, c->stream);
+        else
+            launch_dense_import(dA, lda, n, order, r.A11, c->Ml, c->Nl, c->v,
+                                c->Px, c->Py, r.pi, r.pj, c->stream);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->input_dirty = true;
+    c->n = n;
+    return CONFLUX_LU_OK;
+}
+
+int conflux_lu_logical_order(conflux_lu_ctx *c, int *n) {
+    if (!c || !n) return CONFLUX_LU_EARG;
+    *n = c->n;
+    return CONFLUX_LU_OK;
+}
+
+int conflux_lu_get_factors_device(conflux_lu_ctx *c, double *dF, int64_t ldf,
+                                  int *dperm) {
+    if (!dense_single_process(c) || c->factored_kind == 0 ||
+        (dF && ldf < c->nf))
+        return CONFLUX_LU_EARG;
+    const int n = c->nf;
+    if (dF) {
+        for (auto &r : c->rs) {
+            if (r.pk != 0) continue;
+            if (!r.Fres) return CONFLUX_LU_EARG;
+            launch_dense_export(r.Fres, c->Ml, c->Nl, c->v, c->Px, c->Py, r.pi,
+                                r.pj, dF, ldf, n, c->stream);
+        }
+        HIPCHK(hipGetLastError());
+    }
+    if (dperm) {
+        if ((int)c->pivotInds.size() < n) return CONFLUX_LU_EARG;
+        HIPCHK(hipMemcpyAsync(dperm, c->pivotInds.data(), size_t(n) * 4,
+                              hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return CONFLUX_LU_OK;
+}
+
+int conflux_lu_solve_device(conflux_lu_ctx *c, double *dB, int64_t ldb,
+                            int nrhs, int trans, double *elapsed_ms) {
+    if ((trans != 0 && trans != 1) || nrhs <= 0 || ldb < nrhs)
+        return CONFLUX_LU_EARG;
+    return solve_common(c, false, dB, nrhs, elapsed_ms, trans == 1, ldb);
+}
+
+int conflux_chol_solve_device(conflux_lu_ctx *c, double *dB, int64_t ldb,
+                              int nrhs, double *elapsed_ms) {
+    if (nrhs <= 0 || ldb < nrhs) return CONFLUX_LU_EARG;
+    return solve_common(c, true, dB, nrhs, elapsed_ms, false, ldb);
+}
+
+// {sum log|d_i|, negatives, flags} over the leading nf diagonal entries of
+// the stored factors: every (p, p, 0) rank contributes the diagonal tiles it
+// holds to one nf-vector, one block reduces it in a fixed order.
+static int logdet_common(conflux_lu_ctx *c, bool chol, double out3[3]) {
+    if (int rc = solve_guard(c, chol, out3, 1)) return rc;
+    const int n = c->nf;
+    double *d_diag = nullptr, *d_out = nullptr;
+    auto cleanup = [&]() {
+        if (d_diag) (void)hipFree(d_diag);
+        if (d_out) (void)hipFree(d_out);
+    };
+#define SCHK(x)                                                               \
+    if ((x) != hipSuccess) {                                                  \
+        cleanup();                                                            \
+        return CONFLUX_LU_EHIP;                                               \
+    }
+    SCHK(hipMalloc(&d_diag, size_t(n) * 8));
+    SCHK(hipMalloc(&d_out, 3 * 8));
+    for (int p = 0; p < c->Px; ++p) {
+        RankState *r = c->sim ? get_rs(*c, p, p, 0) : &c->rs[0];
+        if (!r || !r->Fres) {
+            cleanup();
+            return CONFLUX_LU_EARG;
+        }
+        launch_diag_gather(r->Fres, c->Ml, c->Nl, c->v, c->Px, p, n, d_diag,
+                           c->stream);
+    }
+    launch_logdet_reduce(d_diag, n, d_out, c->stream);
+    SCHK(hipGetLastError());
+    SCHK(hipMemcpyAsync(out3, d_out, 3 * 8, hipMemcpyDeviceToHost, c->stream));
+    SCHK(hipStreamSynchronize(c->stream));
+#undef SCHK
+    cleanup();
+    return CONFLUX_LU_OK;
+}
+
+int conflux_lu_slogdet(conflux_lu_ctx *c, double *sign, double *logabsdet) {
+    if (!sign || !logabsdet) return CONFLUX_LU_EARG;
+    double o[3];
+    if (int rc = logdet_common(c, false, o)) return rc;
+    const int flags = (int)o[2];
+    if (flags & 2) {  // a NaN or an infinity on the diagonal
+        *sign = *logabsdet = std::nan("");
+        return CONFLUX_LU_OK;
+    }
+    if (flags & 1) {  // a zero pivot: the matrix is singular
+        *sign = 0.0;
+        *logabsdet = -INFINITY;
+        return CONFLUX_LU_OK;
+    }
+    // det(P): parity of the permutation from its cycle lengths
+    const std::vector<int> &pm = c->pivotInds;
+    std::vector<char> seen(pm.size(), 0);
+    int odd = (int)o[1] & 1;
+    for (size_t i = 0; i < pm.size(); ++i) {
+        if (seen[i]) continue;
+        size_t len = 0;
+        for (size_t j = i; !seen[j]; j = (size_t)pm[j]) {
+            seen[j] = 1;
+            ++len;
+        }
+        odd ^= (int)((len - 1) & 1);
+    }
+    *sign = odd ? -1.0 : 1.0;
+    *logabsdet = o[0];
+    return CONFLUX_LU_OK;
+}
+
+int conflux_chol_logdet(conflux_lu_ctx *c, double *logdet) {
+    if (!logdet) return CONFLUX_LU_EARG;
+    double o[3];
+    if (int rc = logdet_common(c, true, o)) return rc;
+    const int flags = (int)o[2];
+    *logdet = (flags & 2) ? std::nan("") : (flags & 1) ? -INFINITY : 2.0 * o[0];
+    return CONFLUX_LU_OK;
+}
+
+/* test hook (not in the public header): one rank's slice of the input
+ * snapshot the last factorization kept (Ml x Nl, host).  grank is ignored by
+ * the one-rank engine. */
+int conflux_lu_debug_get_input(conflux_lu_ctx *c, int grank, double *local) {
+    if (!dense_single_process(c) || !local) return CONFLUX_LU_EARG;
+    if (!c->sim) grank = 0;
+    if (grank < 0 || grank >= (int)c->rs.size() || !c->rs[grank].A11in)
+        return CONFLUX_LU_EARG;
+    HIPCHK(hipMemcpyAsync(local, c->rs[grank].A11in, i64(c->Ml) * c->Nl * 8,
+                          hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return CONFLUX_LU_OK;
+}
+
 /* Reciprocal condition number 1 / (||A|| ||A^-1||) of the matrix last
  * factored (gecon / pocon): ||A|| from the input snapshot, ||A^-1||
  * estimated by norm1est.hpp from single-RHS solves with A and A^T on the
@@ -3062,6 +3258,13 @@ static int rcond_common(conflux_lu_ctx *c, bool chol, int norm, double *rcond,
     if (int rc = solve_guard(c, chol, rcond, 1)) return rc;
     if (norm != 0 && norm != 1) return CONFLUX_LU_EARG;
     const int64_t N = c->N;
+    // logical order: with n < N the figure describes the caller's n x n
+    // matrix, not blockdiag(A, I) — ||A|| over the leading block only (a
+    // padding column sums to 1 and could win), the estimator at dimension n
+    // with callbacks that zero-extend the vector going in and crop the one
+    // coming out (the padding block of the inverse is the identity and does
+    // not couple to the leading one).  n == N is the path as it always was.
+    const int64_t n = c->nf;
     RankState *r00 = c->sim ? get_rs(*c, 0, 0, 0) : &c->rs[0];
     if (!r00->A11in) return CONFLUX_LU_EARG;
     const bool aliasA = c->Px == 1 && c->Py == 1;
@@ -3083,7 +3286,8 @@ static int rcond_common(conflux_lu_ctx *c, bool chol, int norm, double *rcond,
         cleanup();                                                            \
         return CONFLUX_LU_EHIP;                                               \
     }
-    double &cached = norm == 0 ? c->anorm_one : c->anorm_inf;
+    double &cached = n < N ? c->anorm_lead[norm]
+                           : (norm == 0 ? c->anorm_one : c->anorm_inf);
     if (cached < 0) {  // once per factorization and norm
         int64_t lda = N;
         if (aliasA) {
@@ -3100,10 +3304,10 @@ static int rcond_common(conflux_lu_ctx *c, bool chol, int norm, double *rcond,
         SCHK(hipMalloc(&d_sums, (size_t)N * 8));
         SCHK(hipMalloc(&d_sc, 8));
         if (norm == 0)
-            launch_col_abs_sums(Ag, lda, (int)N, (int)N, d_sums, c->stream);
+            launch_col_abs_sums(Ag, lda, (int)n, (int)n, d_sums, c->stream);
         else
-            launch_row_abs_sums(Ag, lda, (int)N, (int)N, d_sums, c->stream);
-        launch_colmax_abs(d_sums, N, 1, d_sc, c->stream);
+            launch_row_abs_sums(Ag, lda, (int)n, (int)n, d_sums, c->stream);
+        launch_colmax_abs(d_sums, n, 1, d_sc, c->stream);
         double nrm = 0;
         SCHK(hipMemcpyAsync(&nrm, d_sc, 8, hipMemcpyDeviceToHost, c->stream));
         SCHK(hipStreamSynchronize(c->stream));
@@ -3123,13 +3327,15 @@ static int rcond_common(conflux_lu_ctx *c, bool chol, int norm, double *rcond,
     if (!chol) SCHK(hipMalloc(&Bd, (size_t)N * 8));
     hipError_t herr = hipSuccess;  // the callbacks cannot return: first error
     auto up = [&](double *dst, const double *x) {
+        if (herr == hipSuccess && n < N)
+            herr = hipMemsetAsync(dst + n, 0, (size_t)(N - n) * 8, c->stream);
         if (herr == hipSuccess)
-            herr = hipMemcpyAsync(dst, x, (size_t)N * 8,
+            herr = hipMemcpyAsync(dst, x, (size_t)n * 8,
                                   hipMemcpyHostToDevice, c->stream);
     };
     auto down = [&](double *x, const double *src) {
         if (herr == hipSuccess)
-            herr = hipMemcpyAsync(x, src, (size_t)N * 8,
+            herr = hipMemcpyAsync(x, src, (size_t)n * 8,
                                   hipMemcpyDeviceToHost, c->stream);
         if (herr == hipSuccess) herr = hipStreamSynchronize(c->stream);
     };
@@ -3154,8 +3360,8 @@ static int rcond_common(conflux_lu_ctx *c, bool chol, int norm, double *rcond,
     SCHK(hipEventCreate(&e1));
     SCHK(hipEventRecord(e0, c->stream));
     const norm1est::Result est =
-        norm == 0 ? norm1est::estimate((int)N, apply, apply_t)
-                  : norm1est::estimate((int)N, apply_t, apply);
+        norm == 0 ? norm1est::estimate((int)n, apply, apply_t)
+                  : norm1est::estimate((int)n, apply_t, apply);
     SCHK(herr);
     SCHK(hipEventRecord(e1, c->stream));
     SCHK(hipStreamSynchronize(c->stream));

@@ -132,6 +132,29 @@ void launch_colmax_abs(const double *V, int64_t n, int ncols, double *out,
                        hipStream_t s);
 void launch_axpy_masked(double *X, const double *D, const int *mask,
                         int64_t n, int ncols, hipStream_t s);
+// dense_kernels.hip, the device-resident dense interface.  import: one rank
+// buffer dst (Ml x Nl, rank (pi, pj)) <- blockdiag(A, I) from the caller's
+// n x n dA (order 0: dA[i * lda + j], 1: dA[j * lda + i]); export: the
+// inverse map from a rank buffer into dF (row-major, ldf), cropped to n.
+// rhs_stage_in: X (N x nrhs, ld = nrhs) row r <- B row (idx ? idx[r] : r) for
+// r < n, zero below; rhs_stage_out: B row (idx ? idx[r] : r) <- X row r,
+// r < n.  diag_gather: out[g] = the diagonal entries g < n that rank (p, p)
+// holds; logdet_reduce: out3 = {sum log|d_i| (doubled precision, fixed
+// order), count of d_i < 0, 1 * any zero + 2 * any non-finite}.
+void launch_dense_import(const double *dA, int64_t lda, int n, int order,
+                         double *dst, int Ml, int Nl, int v, int Px, int Py,
+                         int pi, int pj, hipStream_t s);
+void launch_dense_export(const double *src, int Ml, int Nl, int v, int Px,
+                         int Py, int pi, int pj, double *dF, int64_t ldf,
+                         int n, hipStream_t s);
+void launch_rhs_stage_in(const double *B, int64_t ldb, int n, const int *idx,
+                         double *X, int64_t N, int nrhs, hipStream_t s);
+void launch_rhs_stage_out(const double *X, int nrhs, int n, const int *idx,
+                          double *B, int64_t ldb, hipStream_t s);
+void launch_diag_gather(const double *F, int Ml, int Nl, int v, int Px, int p,
+                        int n, double *out, hipStream_t s);
+void launch_logdet_reduce(const double *d, int n, double *out3,
+                          hipStream_t s);
 void launch_tril_unit(const double *F, double *L, int64_t n, hipStream_t s);
 void launch_tril_unit_rows(const double *F, int64_t ldf, double *L,
                            int64_t ldl, int rows, int64_t row0, int64_t ncols,

@@ -43,6 +43,14 @@
  *   conflux_chol_rcond              reciprocal condition number (gecon /
  *                                   pocon) from Higham's 1-norm estimator
  *                                   over those solves.
+ *   conflux_lu_set_matrix_device / <-> nothing: the reference's callers fill
+ *   conflux_lu_get_factors_device /    lu_params::data on the host, in its
+ *   conflux_lu_solve_device /          layout.  These take and return the
+ *   conflux_chol_solve_device /        caller's own dense DEVICE buffers, of
+ *   conflux_lu_logical_order           any order n <= N_padded.
+ *   conflux_lu_slogdet /          <-> nothing: sign and log|det| (LU) and
+ *   conflux_chol_logdet               log det (Cholesky) from the stored
+ *                                     diagonal, reduced on device.
  *
  * Ownership: caller owns all host buffers passed in; the engine owns device
  * memory.  Deterministic given (input, grid, v, world).  All functions
@@ -75,9 +83,11 @@ typedef struct conflux_lu_ctx conflux_lu_ctx;
  * v*Px exactly like the reference (lu_params.hpp:67-71): conflux_lu_dims
  * reports the padded size, local buffers are sized for it, and the
  * generator fills the padding the way the reference's InitMatrix does
- * (a caller-supplied matrix should extend the padding with nonsingular
- * data, e.g. the same random fill — zero padding would hit zero pivots,
- * as it would in the reference).
+ * (a caller-supplied matrix in the engine's own layout should extend the
+ * padding with nonsingular data, e.g. the same random fill — zero padding
+ * would hit zero pivots, as it would in the reference;
+ * conflux_lu_set_matrix_device pads by itself, with an identity block that
+ * stays out of the caller's problem).
  *
  * world == Px*Py*Pz processes, one per GPU.  rank r maps to grid coords
  * (pi, pj, pk) = (r / (Py*Pz), (r / Pz) % Py, r % Pz) — the reference's
@@ -244,8 +254,12 @@ int conflux_lu_solve_trans(conflux_lu_ctx *ctx, double *B, int nrhs,
  * within a few percent.  cond(A) ~ 1 / rcond is the number that
  * conflux_lu_solve_refined's "cond(A) well below 2^53" and the no-pivot fast
  * path's "diagonally dominant" ask about.
- * rcond describes the PADDED N_padded x N_padded matrix the engine factored,
- * padding rows and columns included.
+ * After conflux_lu_set_matrix_device with n < N_padded, rcond describes the
+ * caller's n x n matrix: ||A|| is taken over the leading n rows and columns
+ * of the snapshot and the estimator runs at dimension n.  After every other
+ * way of setting the matrix (logical order == N_padded) it describes the
+ * PADDED N_padded x N_padded matrix the engine factored, padding rows and
+ * columns included.
  * rcond = 0 when ||A|| == 0 or the estimate is not finite (a zero pivot) —
  * not an error.
  * anorm (may be NULL): ||A|| in the chosen norm; computed once per
@@ -268,6 +282,88 @@ int conflux_lu_rcond(conflux_lu_ctx *ctx, int norm, double *rcond,
  * after an LU factorization. */
 int conflux_chol_rcond(conflux_lu_ctx *ctx, double *rcond, double *anorm,
                        int *nsolves, double *elapsed_ms);
+
+/* ---- Device-resident dense interface (no reference counterpart) ----------
+ *
+ * Point the engine at a matrix the caller already holds on the device: any
+ * order 1 <= n <= N_padded (whole tiles of padding included), row- or
+ * column-major, no host trip and no re-tiling by the caller.  The engine
+ * factors blockdiag(A, I) of order N_padded.  Tournament pivoting never picks
+ * an all-zero candidate row and the zero-pivot rule never scales by one, so
+ * the identity block is inert: perm[n:] is the identity, F[n:, n:] == I, both
+ * off-diagonal blocks of F are exactly zero, and the padded problem is the
+ * caller's problem plus rows that do not couple to it.
+ *
+ * Pointers and streams: every d* pointer is DEVICE memory owned by the
+ * caller.  The calls enqueue on the engine's own stream and return after
+ * synchronizing it; they do not wait for any other stream, so the caller
+ * must have finished producing the buffers (synchronize the producing stream
+ * first).  Single process only: the one-rank engine (world == 1) and the
+ * simulation grids (rank < 0); world > 1 returns CONFLUX_LU_EARG before any
+ * communication, like the solves.
+ *
+ * Logical order: the context remembers n.  conflux_lu_init_matrix*,
+ * conflux_lu_set_matrix_local and the simulation upload reset it to
+ * N_padded, after which everything behaves as it always did.  What follows
+ * the logical order of the matrix last factored: the *_device calls below,
+ * conflux_lu_slogdet / conflux_chol_logdet and conflux_lu_rcond /
+ * conflux_chol_rcond.  What keeps describing the PADDED matrix:
+ * conflux_lu_validate / conflux_chol_validate (the residual numerator is
+ * unaffected, ||A||_F gains the N_padded - n ones), the host-buffer solves
+ * (B has N_padded rows) and conflux_lu_get_factors.
+ *
+ * conflux_lu_set_matrix_device: dA holds element (i, j) at dA[i * lda + j]
+ * (order 0, row-major) or dA[j * lda + i] (order 1, column-major), lda >= n.
+ * Marks the input fresh exactly as conflux_lu_set_matrix_local does: the
+ * next factor snapshots it, repeated factors restore the snapshot,
+ * conflux_lu_set_pivoting(0) and conflux_chol_factor work unchanged
+ * (blockdiag(SPD, I) is SPD).  Layers pk > 0 are zeroed.
+ * CONFLUX_LU_EARG: dA == NULL, n < 1, n > N_padded, lda < n, order not 0/1,
+ * world > 1. */
+int conflux_lu_set_matrix_device(conflux_lu_ctx *ctx, const double *dA,
+                                 int64_t lda, int n, int order);
+
+/* The logical order of the CURRENT input (N_padded unless the last matrix
+ * came through conflux_lu_set_matrix_device). */
+int conflux_lu_logical_order(conflux_lu_ctx *ctx, int *n);
+
+/* After a store_factors run: the leading n x n block of the factored matrix
+ * (pivoted row order, strict lower = L, upper = U; Cholesky: lower = L) as a
+ * dense row-major device matrix dF (ldf >= n), and/or the leading n entries
+ * of perm as int32 on the device.  Either pointer may be NULL.
+ * CONFLUX_LU_EARG: no stored factorization, ldf < n with dF given,
+ * world > 1. */
+int conflux_lu_get_factors_device(conflux_lu_ctx *ctx, double *dF,
+                                  int64_t ldf, int *dperm);
+
+/* conflux_lu_solve (trans = 0) / conflux_lu_solve_trans (trans = 1) on the
+ * caller's device buffer: dB is n x nrhs, row-major, ldb >= nrhs, overwritten
+ * in place with X; the ldb - nrhs slack of every row is not touched.
+ * elapsed_ms has conflux_lu_solve's meaning; CONFLUX_SOLVE_BLOCK /
+ * CONFLUX_SOLVE_SKINNY apply as there.  The sweeps are the host entry
+ * points' sweeps — with n == N_padded the bits agree.
+ * CONFLUX_LU_EARG: dB == NULL, nrhs <= 0, ldb < nrhs, trans not 0/1, and
+ * every case in which conflux_lu_solve returns it (world > 1 included). */
+int conflux_lu_solve_device(conflux_lu_ctx *ctx, double *dB, int64_t ldb,
+                            int nrhs, int trans, double *elapsed_ms);
+
+/* Same for the last Cholesky run (conflux_chol_solve's guards). */
+int conflux_chol_solve_device(conflux_lu_ctx *ctx, double *dB, int64_t ldb,
+                              int nrhs, double *elapsed_ms);
+
+/* det(A) of the n x n matrix of the last store_factors LU run as
+ * sign * exp(logabsdet): logabsdet = sum log|U_ii| over the leading n
+ * diagonal entries (summed on device in doubled precision, in a fixed order:
+ * two calls agree bitwise), sign = det(P) * prod sign(U_ii) in {-1, +1}.
+ * A zero pivot gives sign = 0, logabsdet = -inf — not an error; a non-finite
+ * pivot gives NaN in both.
+ * CONFLUX_LU_EARG: a NULL output, and conflux_lu_solve's guard cases (no
+ * factorization, store_factors off, a Cholesky run, world > 1). */
+int conflux_lu_slogdet(conflux_lu_ctx *ctx, double *sign, double *logabsdet);
+
+/* log det(A) = 2 * sum log L_ii for the last Cholesky run; EARG after an LU
+ * factorization. */
+int conflux_chol_logdet(conflux_lu_ctx *ctx, double *logdet);
 
 /* Dimensions derived by the engine (reference lu_params.hpp:67-82). */
 int conflux_lu_dims(conflux_lu_ctx *ctx, int *Ml, int *Nl, int *Nt,
