@@ -142,6 +142,19 @@ def _load():
     lib.conflux_chol_logdet.argtypes = [ptr, dbl_p]
     lib.conflux_lu_logical_order.argtypes = [ptr, ctypes.POINTER(i32)]
     lib.conflux_lu_debug_get_input.argtypes = [ptr, i32, ptr]
+    # refined solves: transposed, and on device buffers (berr/ferr are host)
+    i32_p = ctypes.POINTER(i32)
+    lib.conflux_lu_solve_refined_trans.argtypes = \
+        lib.conflux_lu_solve_refined.argtypes
+    lib.conflux_lu_solve_refined_device.argtypes = [
+        ptr, ptr, i64, i32, i32, i32, ptr, ptr, i32_p, dbl_p]
+    lib.conflux_chol_solve_refined_device.argtypes = [
+        ptr, ptr, i64, i32, i32, ptr, ptr, i32_p, dbl_p]
+    lib.conflux_lu_debug_residual_dd_t.argtypes = \
+        lib.conflux_lu_debug_residual_dd.argtypes
+    lib.conflux_lu_debug_residual_t_chunk.argtypes = []
+    lib.conflux_lu_debug_residual_dd_t_bench.argtypes = [
+        i32, i32, i32, i32, dbl_p, dbl_p, dbl_p]
     return lib
 
 
@@ -369,6 +382,16 @@ class Engine:
                                    "solve_cholesky_refined", B, max_iter,
                                    return_info)
 
+    def solve_transposed_refined(self, B, max_iter=10, return_info=False):
+        """solve_transposed() followed by up to max_iter passes of refinement
+        (conflux_lu_solve_refined_trans; same conventions as solve_refined).
+        The residual B - A^T X reads the stored input in place, berr takes
+        ||A||1.  max_iter=0 is solve_transposed bit for bit.  Raises
+        ConfluxLuError after factor_cholesky()."""
+        return self._solve_refined(lib().conflux_lu_solve_refined_trans,
+                                   "solve_transposed_refined", B, max_iter,
+                                   return_info)
+
     # ---- device-resident dense interface --------------------------------
     # Pointers are raw device addresses (e.g. torch.Tensor.data_ptr()); the
     # caller owns the buffers and must have finished producing them — the
@@ -415,6 +438,38 @@ class Engine:
                                              ctypes.byref(ms)),
              "solve_cholesky_device")
         return ms.value
+
+    def _refined_device(self, what, call, nrhs, max_iter):
+        import numpy as np
+        berr = np.zeros(max(int(nrhs), 0))
+        ferr = np.zeros(max(int(nrhs), 0))
+        iters = ctypes.c_int()
+        ms = ctypes.c_double()
+        _chk(call(int(max_iter), berr.ctypes.data_as(ctypes.c_void_p),
+                  ferr.ctypes.data_as(ctypes.c_void_p), ctypes.byref(iters),
+                  ctypes.byref(ms)), what)
+        return dict(berr=berr, ferr=ferr, iters=iters.value, ms=ms.value)
+
+    def solve_refined_device(self, dB, ldb, nrhs, trans=False, max_iter=10):
+        """solve_refined (solve_transposed_refined with trans) in place on the
+        device buffer dB (n x nrhs, row-major, ldb >= nrhs; the slack is not
+        touched).  Everything describes the n x n matrix of the logical
+        order.  Returns the info dict of solve_refined: berr and ferr as
+        numpy arrays, iters, ms."""
+        return self._refined_device(
+            "solve_refined_device",
+            lambda *a: lib().conflux_lu_solve_refined_device(
+                self._h, dB, ldb, nrhs, int(bool(trans)), *a),
+            nrhs, max_iter)
+
+    def solve_cholesky_refined_device(self, dB, ldb, nrhs, max_iter=10):
+        """solve_refined_device for the factor of the last
+        factor_cholesky(); both triangles of the input must hold A."""
+        return self._refined_device(
+            "solve_cholesky_refined_device",
+            lambda *a: lib().conflux_chol_solve_refined_device(
+                self._h, dB, ldb, nrhs, *a),
+            nrhs, max_iter)
 
     def slogdet(self):
         """(sign, log|det A|) of the n x n matrix of the last factor(), like

@@ -3416,30 +3416,49 @@ int conflux_chol_rcond(conflux_lu_ctx *c, double *rcond, double *anorm,
  * computed on first use and cached until the next factorization.  F and
  * perm are staged once per call; every pass reuses them.
  *
- * Determinism: the residual kernel combines its partial accumulators in an
- * order fixed by lane ids, the maxima are exact, so two calls agree
- * bitwise. */
+ * Determinism: the residual kernels combine their partial accumulators in an
+ * order fixed by lane, wave and chunk indices, the maxima are exact, so two
+ * calls agree bitwise.
+ *
+ * trans (LU only): the same loop on A^T X = B.  solve() is the transposed
+ * solve — sweeps in place, then the scatter X[perm[r]] = Z[r] — the residual
+ * B - A^T X comes from launch_residual_dd_t on the same snapshot, read in
+ * place (its workspace is row-chunks x N x column-group, not N^2), and berr
+ * takes ||A^T||inf = ||A||1, the norm the condition estimate caches.
+ *
+ * Two kinds of B, as in solve_common.  Host (ldb == 0): N_padded x nrhs, and
+ * everything describes the padded matrix, as it always did.  Device
+ * (ldb >= nrhs): the caller's nf x nrhs window; it is kept, zero-extended to
+ * N rows, for the residual (X overwrites the window), and everything
+ * describes the caller's nf x nf matrix: the norm is the leading block's,
+ * the residual runs over the leading nf rows and columns, and the padding
+ * rows of X, R and D stay exactly zero (R's are zeroed once and never
+ * written, the sweeps map zero rows to zero rows), so they cannot win a
+ * column maximum.  With nf == N the two describe the same thing, launch for
+ * launch. */
 static int solve_refined_common(conflux_lu_ctx *c, bool chol, double *B,
                                 int nrhs, int max_iter, double *berr,
-                                double *ferr, int *iters,
-                                double *elapsed_ms) {
+                                double *ferr, int *iters, double *elapsed_ms,
+                                bool trans = false, int64_t ldb = 0) {
     if (int rc = solve_guard(c, chol, B, nrhs)) return rc;
     if (max_iter < 0) return CONFLUX_LU_EARG;
     const int64_t N = c->N;
+    const bool dev = ldb > 0;
+    const int64_t m = dev ? c->nf : N;  // the order everything describes
     RankState *r00 = c->sim ? get_rs(*c, 0, 0, 0) : &c->rs[0];
     if (!r00->A11in) return CONFLUX_LU_EARG;
     const bool aliasA = c->Px == 1 && c->Py == 1;
 
     SolveDev sd;
     double *Ag = nullptr, *Bd = nullptr, *Xd = nullptr, *Rd = nullptr,
-           *Dd = nullptr, *d_sc = nullptr, *d_rows = nullptr;
+           *Dd = nullptr, *d_sc = nullptr, *d_rows = nullptr, *d_ws = nullptr;
     int *d_mask = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     auto cleanup = [&]() {
         sd.release();
         if (Ag && !aliasA) (void)hipFree(Ag);
         if (Dd && Dd != Rd) (void)hipFree(Dd);
-        for (double *p : {Bd, Xd, Rd, d_sc, d_rows})
+        for (double *p : {Bd, Xd, Rd, d_sc, d_rows, d_ws})
             if (p) (void)hipFree(p);
         if (d_mask) (void)hipFree(d_mask);
         if (e0) (void)hipEventDestroy(e0);
@@ -3476,7 +3495,13 @@ static int solve_refined_common(conflux_lu_ctx *c, bool chol, double *B,
         SCHK(hipMalloc(&Dd, xb));
     SCHK(hipMalloc(&d_sc, (size_t)nrhs * 8));
     SCHK(hipMalloc(&d_mask, (size_t)nrhs * 4));
-    SCHK(hipMemcpyAsync(Bd, B, xb, hipMemcpyHostToDevice, c->stream));
+    if (trans)
+        SCHK(hipMalloc(&d_ws, residual_dd_t_ws_bytes((int)m, (int)m, nrhs)));
+    if (dev)
+        launch_rhs_stage_in(B, ldb, (int)m, nullptr, Bd, N, nrhs, c->stream);
+    else
+        SCHK(hipMemcpyAsync(Bd, B, xb, hipMemcpyHostToDevice, c->stream));
+    if (m < N) SCHK(hipMemsetAsync(Rd, 0, xb, c->stream));
 
     std::vector<double> xmax(nrhs), bmax(nrhs), rmax(nrhs), dmax(nrhs),
         dprev(nrhs, 0.0), be(nrhs, 0.0), fe(nrhs, 0.0);
@@ -3489,33 +3514,59 @@ static int solve_refined_common(conflux_lu_ctx *c, bool chol, double *B,
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         return e;
     };
-    if (c->anorm_inf < 0) {  // once per factorization
+    // ||A||inf, or ||A^T||inf = ||A||1, of the order-m matrix: the slots the
+    // condition estimate fills, once per factorization
+    double &cached = m < N ? c->anorm_lead[trans ? 0 : 1]
+                           : (trans ? c->anorm_one : c->anorm_inf);
+    if (cached < 0) {
         SCHK(hipMalloc(&d_rows, (size_t)N * 8));
-        launch_row_abs_sums(Ag, lda, (int)N, (int)N, d_rows, c->stream);
-        launch_colmax_abs(d_rows, N, 1, d_sc, c->stream);
+        if (trans)
+            launch_col_abs_sums(Ag, lda, (int)m, (int)m, d_rows, c->stream);
+        else
+            launch_row_abs_sums(Ag, lda, (int)m, (int)m, d_rows, c->stream);
+        launch_colmax_abs(d_rows, m, 1, d_sc, c->stream);
         double nrm = 0;
         SCHK(hipMemcpyAsync(&nrm, d_sc, 8, hipMemcpyDeviceToHost, c->stream));
         SCHK(hipStreamSynchronize(c->stream));
-        c->anorm_inf = nrm;
+        cached = nrm;
     }
-    const double anorm = c->anorm_inf;
+    const double anorm = cached;
     SCHK(colmax(Bd, bmax));
 
+    // dst <- solve(src), dst != src unless Cholesky.  trans sweeps in place
+    // on src (clobbered) and scatters into dst.
+    auto solve_into = [&](double *src, double *dst) {
+        if (trans) {
+            solve_sweeps(c, false, sd, src, nrhs, true);
+            launch_row_scatter(src, nrhs, dst, nrhs, sd.d_pm, (int)N, nrhs,
+                               c->stream);
+            return 0;
+        }
+        if (solve_permute(c, chol, sd, src, dst, nrhs)) return 1;
+        solve_sweeps(c, chol, sd, dst, nrhs);
+        return 0;
+    };
     SCHK(hipEventCreate(&e0));
     SCHK(hipEventCreate(&e1));
     SCHK(hipEventRecord(e0, c->stream));
-    if (solve_permute(c, chol, sd, Bd, Xd, nrhs)) {
+    // trans: B goes through Rd, which the first residual overwrites anyway
+    if (trans)
+        SCHK(hipMemcpyAsync(Rd, Bd, xb, hipMemcpyDeviceToDevice, c->stream));
+    if (solve_into(trans ? Rd : Bd, Xd)) {
         cleanup();
         return CONFLUX_LU_EHIP;
     }
-    solve_sweeps(c, chol, sd, Xd, nrhs);
     SCHK(colmax(Xd, xmax));
 
     const double u = 0x1p-53;
     int it = 0, applied_passes = 0;
     for (;;) {
-        launch_residual_dd(Ag, lda, Xd, Bd, Rd, (int)N, (int)N, nrhs,
-                           c->stream);
+        if (trans)
+            (void)launch_residual_dd_t(Ag, lda, Xd, Bd, Rd, (int)m, (int)m,
+                                       nrhs, c->stream, d_ws);
+        else
+            launch_residual_dd(Ag, lda, Xd, Bd, Rd, (int)m, (int)m, nrhs,
+                               c->stream);
         SCHK(colmax(Rd, rmax));
         int nactive = 0;
         for (int j = 0; j < nrhs; ++j) {
@@ -3525,11 +3576,10 @@ static int solve_refined_common(conflux_lu_ctx *c, bool chol, double *B,
             nactive += active[j];
         }
         if (it == max_iter || nactive == 0) break;
-        if (solve_permute(c, chol, sd, Rd, Dd, nrhs)) {
+        if (solve_into(Rd, Dd)) {
             cleanup();
             return CONFLUX_LU_EHIP;
         }
-        solve_sweeps(c, chol, sd, Dd, nrhs);
         SCHK(colmax(Dd, dmax));
         int napplied = 0;
         for (int j = 0; j < nrhs; ++j) {
@@ -3558,7 +3608,10 @@ static int solve_refined_common(conflux_lu_ctx *c, bool chol, double *B,
         ++applied_passes;
     }
     SCHK(hipEventRecord(e1, c->stream));
-    SCHK(hipMemcpyAsync(B, Xd, xb, hipMemcpyDeviceToHost, c->stream));
+    if (dev)
+        launch_rhs_stage_out(Xd, nrhs, (int)m, nullptr, B, ldb, c->stream);
+    else
+        SCHK(hipMemcpyAsync(B, Xd, xb, hipMemcpyDeviceToHost, c->stream));
     SCHK(hipStreamSynchronize(c->stream));
     SCHK(hipGetLastError());
     if (berr) std::copy(be.begin(), be.end(), berr);
@@ -3586,6 +3639,32 @@ int conflux_chol_solve_refined(conflux_lu_ctx *c, double *B, int nrhs,
                                int *iters, double *elapsed_ms) {
     return solve_refined_common(c, true, B, nrhs, max_iter, berr, ferr, iters,
                                 elapsed_ms);
+}
+
+int conflux_lu_solve_refined_trans(conflux_lu_ctx *c, double *B, int nrhs,
+                                   int max_iter, double *berr, double *ferr,
+                                   int *iters, double *elapsed_ms) {
+    return solve_refined_common(c, false, B, nrhs, max_iter, berr, ferr,
+                                iters, elapsed_ms, true);
+}
+
+int conflux_lu_solve_refined_device(conflux_lu_ctx *c, double *dB, int64_t ldb,
+                                    int nrhs, int trans, int max_iter,
+                                    double *berr, double *ferr, int *iters,
+                                    double *elapsed_ms) {
+    if ((trans != 0 && trans != 1) || nrhs <= 0 || ldb < nrhs)
+        return CONFLUX_LU_EARG;
+    return solve_refined_common(c, false, dB, nrhs, max_iter, berr, ferr,
+                                iters, elapsed_ms, trans == 1, ldb);
+}
+
+int conflux_chol_solve_refined_device(conflux_lu_ctx *c, double *dB,
+                                      int64_t ldb, int nrhs, int max_iter,
+                                      double *berr, double *ferr, int *iters,
+                                      double *elapsed_ms) {
+    if (nrhs <= 0 || ldb < nrhs) return CONFLUX_LU_EARG;
+    return solve_refined_common(c, true, dB, nrhs, max_iter, berr, ferr,
+                                iters, elapsed_ms, false, ldb);
 }
 
 int conflux_lu_get_factors(conflux_lu_ctx *c, double *F_local, int *perm) {
@@ -4303,6 +4382,45 @@ int conflux_lu_debug_residual_group_width() {
     return conflux_residual_group_width();
 }
 
+// R (K x nrhs) = B - A^T X, A (M x lda host, K columns used), X (M x nrhs),
+// with the doubled-precision accumulator; A is uploaded as it lies and read
+// in place
+int conflux_lu_debug_residual_dd_t(int M, int K, int nrhs, int64_t lda,
+                                   const double *A, const double *X,
+                                   const double *B, double *R) {
+    if (M <= 0 || nrhs <= 0 || K <= 0 || lda < K || !A || !X || !B || !R)
+        return CONFLUX_LU_EARG;
+    double *dA = nullptr, *dX = nullptr, *dB = nullptr, *dR = nullptr;
+    auto cleanup = [&]() {
+        for (double *p : {dA, dX, dB, dR})
+            if (p) (void)hipFree(p);
+    };
+    hipError_t e = hipMalloc(&dA, i64(M) * lda * 8);
+    if (e == hipSuccess) e = hipMalloc(&dX, i64(M) * nrhs * 8);
+    if (e == hipSuccess) e = hipMalloc(&dB, i64(K) * nrhs * 8);
+    if (e == hipSuccess) e = hipMalloc(&dR, i64(K) * nrhs * 8);
+    if (e == hipSuccess)
+        e = hipMemcpy(dA, A, i64(M) * lda * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMemcpy(dX, X, i64(M) * nrhs * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMemcpy(dB, B, i64(K) * nrhs * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        if (launch_residual_dd_t(dA, lda, dX, dB, dR, M, K, nrhs, nullptr))
+            e = hipErrorOutOfMemory;
+        else
+            e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess)
+        e = hipMemcpy(R, dR, i64(K) * nrhs * 8, hipMemcpyDeviceToHost);
+    cleanup();
+    HIPCHK(e);
+    return CONFLUX_LU_OK;
+}
+
+int conflux_lu_debug_residual_t_chunk() { return conflux_residual_t_chunk(); }
+
 /* Device-only timing of the residual (tools/solve_bench.py --refine):
  * ms_resid = mean ms of one R = B - A X over an M x K matrix and nrhs
  * columns (ceil(nrhs / group width) passes over A); ms_copy = mean ms of a
@@ -4350,6 +4468,69 @@ int conflux_lu_debug_residual_dd_bench(int M, int K, int nrhs, int iters,
     (void)hipFree(dB); (void)hipFree(dR);
     (void)hipEventDestroy(a); (void)hipEventDestroy(b);
     (void)hipStreamDestroy(s);
+    return CONFLUX_LU_OK;
+}
+
+/* The same for the transposed residual (tools/solve_bench.py --refine
+ * --trans): ms_resid_t = mean ms of one R = B - A^T X over the M x K matrix
+ * (workspace allocated once, outside the timed window), ms_resid = one plain
+ * R = B - A X over the same matrix, ms_copy = the device copy of its bytes —
+ * all three in one run, on one buffer. */
+int conflux_lu_debug_residual_dd_t_bench(int M, int K, int nrhs, int iters,
+                                         double *ms_resid_t, double *ms_resid,
+                                         double *ms_copy) {
+    if (M <= 0 || K <= 0 || nrhs <= 0 || iters <= 0 || !ms_resid_t ||
+        !ms_resid || !ms_copy)
+        return CONFLUX_LU_EARG;
+    hipStream_t s;
+    HIPCHK(hipStreamCreate(&s));
+    const int L = std::max(M, K);
+    double *dA, *dA2, *dX, *dB, *dR, *dW;
+    HIPCHK(hipMalloc(&dA, i64(M) * K * 8));
+    HIPCHK(hipMalloc(&dA2, i64(M) * K * 8));
+    HIPCHK(hipMalloc(&dX, i64(L) * nrhs * 8));
+    HIPCHK(hipMalloc(&dB, i64(L) * nrhs * 8));
+    HIPCHK(hipMalloc(&dR, i64(L) * nrhs * 8));
+    HIPCHK(hipMalloc(&dW, residual_dd_t_ws_bytes(M, K, nrhs)));
+    launch_init_matrix(dA, M, K, K, 1, 1, 0, 0, 0, 7, s);
+    launch_init_matrix(dX, L, nrhs, nrhs, 1, 1, 0, 0, 0, 8, s);
+    launch_init_matrix(dB, L, nrhs, nrhs, 1, 1, 0, 0, 0, 9, s);
+    hipEvent_t a, b;
+    HIPCHK(hipEventCreate(&a));
+    HIPCHK(hipEventCreate(&b));
+    auto timed = [&](auto &&run, double *out) -> int {
+        float ms = 0;
+        run();  // warmup
+        HIPCHK(hipEventRecord(a, s));
+        for (int i = 0; i < iters; ++i) run();
+        HIPCHK(hipEventRecord(b, s));
+        HIPCHK(hipEventSynchronize(b));
+        HIPCHK(hipEventElapsedTime(&ms, a, b));
+        *out = ms / iters;
+        return CONFLUX_LU_OK;
+    };
+    int rc = timed(
+        [&] {
+            (void)launch_residual_dd_t(dA, K, dX, dB, dR, M, K, nrhs, s, dW);
+        },
+        ms_resid_t);
+    if (!rc)
+        rc = timed(
+            [&] { launch_residual_dd(dA, K, dX, dB, dR, M, K, nrhs, s); },
+            ms_resid);
+    if (!rc)
+        rc = timed(
+            [&] {
+                (void)hipMemcpyAsync(dA2, dA, i64(M) * K * 8,
+                                     hipMemcpyDeviceToDevice, s);
+            },
+            ms_copy);
+    const hipError_t e = hipGetLastError();
+    for (double *p : {dA, dA2, dX, dB, dR, dW}) (void)hipFree(p);
+    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
+    (void)hipStreamDestroy(s);
+    if (rc) return rc;
+    HIPCHK(e);
     return CONFLUX_LU_OK;
 }
 

@@ -126,6 +126,17 @@ void launch_residual_dd(const double *A, int64_t lda, const double *X,
                         const double *B, double *R, int M, int K, int nrhs,
                         hipStream_t s);
 int conflux_residual_group_width();
+// R (K x nrhs) = B - A^T X in doubled precision, A stored M x K and read in
+// place, X (M x nrhs), B and R (K x nrhs), ld = nrhs; same column groups.
+// The row reduction is cut into conflux_residual_t_chunk()-row chunks whose
+// partials go through ws (residual_dd_t_ws_bytes(M, K, nrhs) bytes of device
+// memory); ws == nullptr allocates and frees one and then synchronises s.
+// Returns 0, or -1 when that allocation or synchronisation fails.
+int launch_residual_dd_t(const double *A, int64_t lda, const double *X,
+                         const double *B, double *R, int M, int K, int nrhs,
+                         hipStream_t s, double *ws = nullptr);
+size_t residual_dd_t_ws_bytes(int M, int K, int nrhs);
+int conflux_residual_t_chunk();
 void launch_row_abs_sums(const double *A, int64_t lda, int M, int K,
                          double *out, hipStream_t s);
 void launch_colmax_abs(const double *V, int64_t n, int ncols, double *out,

@@ -25,6 +25,10 @@
 //   k_residual_dd         R (M x nrhs) = B - A (M x K) X (K x nrhs) with a
 //                         doubled-precision accumulator (dd.hpp), one
 //                         rounding per entry; vector ALU, bandwidth-bound.
+//   k_residual_dd_t_part / _finish
+//                         R (K x nrhs) = B - A^T X on the same stored A: the
+//                         reduction over rows split across waves and blocks,
+//                         partials merged in an order fixed by indices.
 //   k_row_abs_sums, k_colmax_abs, k_axpy_masked
 //                         ||A||inf, per-column max|.| and the masked X += D
 //                         of the refinement loop.
@@ -519,6 +523,172 @@ __global__ __launch_bounds__(256) void k_residual_dd(
         }
 }
 
+// ---------------------------------------------------------------------------
+// Transposed extra-precise residual R (K x nrhs) = B - A^T X, A stored M x K
+// and read IN PLACE along its stored rows (no transposed copy), X (M x nrhs):
+//     R[j][c] = round(B[j][c] - sum_i A[i][j] X[i][c]),
+// every product and addition through dd.hpp, one rounding per entry — the
+// residual of the refined A^T X = B solve.  k_residual_dd cannot serve: it
+// reduces along a stored row, across lanes; here the reduction runs DOWN the
+// rows and each lane owns output entries.
+//
+// Work split, two kernels.
+//   k_residual_dd_t_part   a block owns RT_W = 128 columns x RT_CH = 256 rows
+//       of A.  Lane l of every wave owns the column pair j = 128 strip + 2 l
+//       (one 16-byte load per row; a wave reads 1 KiB contiguous per row) and
+//       accumulates its two columns in registers; wave w takes the rows
+//       16 t + 4 w + u (u < 4) of the chunk, four rows per step, the next
+//       step's loads issued before the current one is consumed.  X[i][c] is
+//       the same for all lanes of a wave: the row index is built from
+//       readfirstlane(wave), so the compiler fetches it with scalar loads
+//       into SGPRs (checked in the ISA: one s_load_dwordx2 per row and
+//       column, no vector load of X).
+//       One lane per column pair alone would give K / 128 waves — 128 at
+//       16384 — hence the split of the reduction over waves and blocks:
+//       16384^2 gives 128 x 64 blocks, 32768 waves.
+//       The four waves' partial (s, c) pairs meet in LDS and wave 0 writes
+//       the block's partial to the workspace W[chunk][column][j].
+//   k_residual_dd_t_finish one thread per (j, column): B[j][c] is the
+//       accumulator's initial value, the chunks' partials are merged into it
+//       and the pair is rounded once.
+// Workspace: ceil(M / 256) x min(nrhs, RES_G) x K pairs of doubles —
+// 1 / 16 of A's bytes per column at most, written once and read once.
+//
+// WHAT FIXES THE MERGE ORDER.  Nothing but indices: a lane adds its rows in
+// ascending row order; wave 0 merges the waves' pairs as ((w0 + w1) + w2) +
+// w3 after a barrier; the finish thread merges the chunks as (((B + p0) +
+// p1) + ...) in ascending chunk index, after the part kernel has completed
+// (stream order).  Every partial has exactly one writer and is complete
+// before it is read; there are no atomics and no flags, so neither the
+// grid's scheduling nor the launch width can change a bit, and two calls
+// agree bitwise.  A column's arithmetic does not involve the other columns
+// of its group, so its bits do not depend on nrhs or on the group it is in.
+//
+// Column group: RES_G = 4, as for k_residual_dd, for the same reason — a
+// pass is ALU-bound at 4 columns (10 * 4 operations per 8 bytes of A), so a
+// wider group buys no bandwidth and costs registers (measured at 16384^2:
+// 0.37 ms at NC = 1, the speed of the memory and 0.89 x k_residual_dd's
+// pass of the same run; 0.57 ms at NC = 4).  The compiler's
+// resource usage (-Rpass-analysis=kernel-resource-usage) of the part kernel
+// for NC = 1 / 2 / 3 / 4, FAST and scalar path alike: 64 / 80 / 96 / 114
+// VGPRs, 8 / 6 / 5 / 4 waves per SIMD, 6 / 12 / 18 / 24 KiB of LDS per
+// block, no VGPR or SGPR spill, no scratch (two accumulator pairs per column
+// instead of k_residual_dd's four, hence more waves than its 5 / 4 / 4 /
+// 3).  The finish kernel: 58 VGPRs, 8 waves, no LDS, no scratch.
+//
+// FAST: A 16-byte aligned and lda even, so every lane's pair is one 16-byte
+// load; otherwise, and for the last column of an odd K, scalar loads.
+// Bounds: columns j >= K and rows i >= M are never read (a lane without a
+// column accumulates zeros and stores nothing; a row past M is skipped by a
+// wave-uniform branch, so X is not read there either); W and R are written
+// inside K only.  All four waves reach the one barrier.
+// ---------------------------------------------------------------------------
+#define RT_CH 256
+#define RT_W 128
+template <int NC, bool FAST>
+__global__ __launch_bounds__(256) void k_residual_dd_t_part(
+    const double *__restrict__ A, int64_t lda, const double *__restrict__ X,
+    double2 *__restrict__ W, int M, int K, int nrhs, int c0) {
+    __shared__ double2 sP[3][NC][RT_W];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int j0 = blockIdx.x * RT_W + lane * 2;
+    const int r0 = blockIdx.y * RT_CH;
+    const int rend = min(r0 + RT_CH, M);
+    dd::Acc acc[2][NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+        acc[0][c] = acc[1][c] = dd::Acc{0.0, 0.0};
+    double ra[2][4][2];   // [buffer][row u][element of the pair]
+    double rx[2][4][NC];  // wave-uniform: SGPRs
+    auto load_step = [&](int st, int buf) {
+        const int rb = r0 + st * 16 + wave * 4;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int row = rb + u;
+            ra[buf][u][0] = ra[buf][u][1] = 0.0;
+            if (row < rend) {  // wave-uniform
+                const double *ap = A + (int64_t)row * lda + j0;
+                if (FAST && j0 + 1 < K) {
+                    const double2 v = *(const double2 *)ap;
+                    ra[buf][u][0] = v.x;
+                    ra[buf][u][1] = v.y;
+                } else {
+                    if (j0 < K) ra[buf][u][0] = ap[0];
+                    if (j0 + 1 < K) ra[buf][u][1] = ap[1];
+                }
+#pragma unroll
+                for (int c = 0; c < NC; ++c)
+                    rx[buf][u][c] = X[(int64_t)row * nrhs + c0 + c];
+            }
+        }
+    };
+    auto consume = [&](int st, int buf) {
+        const int rb = r0 + st * 16 + wave * 4;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (rb + u < rend) {  // wave-uniform
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    dd::add_product(acc[0][c], -ra[buf][u][0], rx[buf][u][c]);
+                    dd::add_product(acc[1][c], -ra[buf][u][1], rx[buf][u][c]);
+                }
+            }
+        }
+    };
+    const int nsteps = (rend - r0 + 15) / 16;
+    load_step(0, 0);
+    for (int st = 0; st < nsteps; st += 2) {
+        // two steps per trip so the register buffers index statically
+        if (st + 1 < nsteps) load_step(st + 1, 1);
+        consume(st, 0);
+        if (st + 1 < nsteps) {
+            if (st + 2 < nsteps) load_step(st + 2, 0);
+            consume(st + 1, 1);
+        }
+    }
+    if (wave > 0) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+#pragma unroll
+            for (int e = 0; e < 2; ++e)
+                sP[wave - 1][c][lane * 2 + e] =
+                    make_double2(acc[e][c].s, acc[e][c].c);
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+#pragma unroll
+                for (int w = 0; w < 3; ++w) {  // ((w0 + w1) + w2) + w3
+                    const double2 p = sP[w][c][lane * 2 + e];
+                    dd::merge(acc[e][c], dd::Acc{p.x, p.y});
+                }
+                if (j0 + e < K)
+                    W[((int64_t)blockIdx.y * NC + c) * K + j0 + e] =
+                        make_double2(acc[e][c].s, acc[e][c].c);
+            }
+    }
+}
+
+// R[j][c0 + c] = round(((B[j][c0 + c] + p_0) + p_1) + ... ), p_ch = W[ch][c][j]:
+// one thread per (j, c), threads along j so the 16-byte reads of W coalesce.
+__global__ __launch_bounds__(64) void k_residual_dd_t_finish(
+    const double2 *__restrict__ W, const double *__restrict__ B,
+    double *__restrict__ R, int K, int nrhs, int c0, int nc, int nchunks) {
+    const int j = blockIdx.x * 64 + threadIdx.x, c = blockIdx.y;
+    if (j >= K) return;
+    dd::Acc acc{B[(int64_t)j * nrhs + c0 + c], 0.0};
+#pragma unroll 8
+    for (int ch = 0; ch < nchunks; ++ch) {
+        const double2 p = W[((int64_t)ch * nc + c) * K + j];
+        dd::merge(acc, dd::Acc{p.x, p.y});
+    }
+    R[(int64_t)j * nrhs + c0 + c] = dd::round(acc);
+}
+
 // out[row] = sum_k |A[row][k]|: one wave per row, lanes along k, butterfly in
 // a fixed order.  max over the rows (k_colmax_abs) gives ||A||inf.
 __global__ __launch_bounds__(256) void k_row_abs_sums(
@@ -707,6 +877,73 @@ void launch_residual_dd(const double *A, int64_t lda, const double *X,
                                          fast, s);
         }
     }
+}
+
+template <int NC>
+static void launch_residual_t_group(const double *A, int64_t lda,
+                                    const double *X, const double *B,
+                                    double *R, double2 *W, int M, int K,
+                                    int nrhs, int c0, bool fast,
+                                    hipStream_t s) {
+    const int nchunks = (M + RT_CH - 1) / RT_CH;
+    const dim3 grid((unsigned)((K + RT_W - 1) / RT_W), (unsigned)nchunks);
+    if (fast)
+        hipLaunchKernelGGL((k_residual_dd_t_part<NC, true>), grid, dim3(256),
+                           0, s, A, lda, X, W, M, K, nrhs, c0);
+    else
+        hipLaunchKernelGGL((k_residual_dd_t_part<NC, false>), grid, dim3(256),
+                           0, s, A, lda, X, W, M, K, nrhs, c0);
+    hipLaunchKernelGGL(k_residual_dd_t_finish,
+                       dim3((unsigned)((K + 63) / 64), (unsigned)NC), dim3(64),
+                       0, s, W, B, R, K, nrhs, c0, NC, nchunks);
+}
+
+int conflux_residual_t_chunk() { return RT_CH; }
+
+size_t residual_dd_t_ws_bytes(int M, int K, int nrhs) {
+    if (M <= 0 || K <= 0 || nrhs <= 0) return 0;
+    return (size_t)((M + RT_CH - 1) / RT_CH) * std::min(RES_G, nrhs) * K *
+           sizeof(double2);
+}
+
+int launch_residual_dd_t(const double *A, int64_t lda, const double *X,
+                         const double *B, double *R, int M, int K, int nrhs,
+                         hipStream_t s, double *ws) {
+    if (M <= 0 || K <= 0 || nrhs <= 0) return 0;
+    double *own = nullptr;
+    if (!ws) {
+        if (hipMalloc(&own, residual_dd_t_ws_bytes(M, K, nrhs)) != hipSuccess)
+            return -1;
+        ws = own;
+    }
+    double2 *W = reinterpret_cast<double2 *>(ws);
+    const bool fast = lda % 2 == 0 && ((uintptr_t)A & 15) == 0;
+    // one pass over A per group; the groups share W in stream order
+    for (int c0 = 0; c0 < nrhs; c0 += RES_G) {
+        switch (std::min(RES_G, nrhs - c0)) {
+            case 4:
+                launch_residual_t_group<4>(A, lda, X, B, R, W, M, K, nrhs, c0,
+                                           fast, s);
+                break;
+            case 3:
+                launch_residual_t_group<3>(A, lda, X, B, R, W, M, K, nrhs, c0,
+                                           fast, s);
+                break;
+            case 2:
+                launch_residual_t_group<2>(A, lda, X, B, R, W, M, K, nrhs, c0,
+                                           fast, s);
+                break;
+            default:
+                launch_residual_t_group<1>(A, lda, X, B, R, W, M, K, nrhs, c0,
+                                           fast, s);
+        }
+    }
+    if (own) {  // hipFree waits for the kernels that use it
+        const hipError_t e = hipStreamSynchronize(s);
+        (void)hipFree(own);
+        if (e != hipSuccess) return -1;
+    }
+    return 0;
 }
 
 void launch_row_abs_sums(const double *A, int64_t lda, int M, int K,

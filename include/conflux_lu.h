@@ -39,6 +39,9 @@
  *   conflux_lu_solve_trans      <-> nothing: the reference has no solve.  A^T X
  *                                   = B on the same stored factors (getrs with
  *                                   trans = 'T'), read in place.
+ *   conflux_lu_solve_refined_trans /   <-> nothing: the refinement for A^T X
+ *   conflux_lu_solve_refined_device /      = B, and all of it on the caller's
+ *   conflux_chol_solve_refined_device      device buffers.
  *   conflux_lu_rcond /          <-> nothing: the reference has no solve.  The
  *   conflux_chol_rcond              reciprocal condition number (gecon /
  *                                   pocon) from Higham's 1-norm estimator
@@ -243,6 +246,26 @@ int conflux_chol_solve_refined(conflux_lu_ctx *ctx, double *B, int nrhs,
 int conflux_lu_solve_trans(conflux_lu_ctx *ctx, double *B, int nrhs,
                            double *elapsed_ms);
 
+/* conflux_lu_solve_refined for A^T X = B: X = conflux_lu_solve_trans(B), the
+ * residual R = B - A^T X in doubled precision, D = conflux_lu_solve_trans(R),
+ * the same decision rules.  The residual reads the input snapshot in place,
+ * along its stored rows — no transposed copy, so a Px = Py = 1 run still
+ * allocates no N^2 buffer; its reduction over the rows is split over the
+ * grid through a workspace of N_padded / 256 partial vectors per column of a
+ * group, merged in an order fixed by indices alone.
+ * Every convention of conflux_lu_solve_refined holds (B host, N_padded x
+ * nrhs, overwritten with X; berr, ferr, iters, elapsed_ms; deterministic;
+ * factors and snapshot only read), with two differences: berr's norm is
+ * ||A^T||inf = ||A||1, the figure conflux_lu_rcond(norm = 0) caches, and
+ * max_iter = 0 gives X bitwise equal to conflux_lu_solve_trans.
+ * CONFLUX_LU_EARG: max_iter < 0 and every case in which
+ * conflux_lu_solve_trans returns it — after a Cholesky run included (there
+ * A = A^T: conflux_chol_solve_refined) and world > 1, before any
+ * communication. */
+int conflux_lu_solve_refined_trans(conflux_lu_ctx *ctx, double *B, int nrhs,
+                                   int max_iter, double *berr, double *ferr,
+                                   int *iters, double *elapsed_ms);
+
 /* Reciprocal condition number of the matrix of the last store_factors LU
  * run (gecon): rcond = 1 / (||A|| * est||A^-1||) in the 1-norm (norm = 0) or
  * the infinity norm (norm = 1).  The reference has no counterpart.  ||A|| is
@@ -305,7 +328,9 @@ int conflux_chol_rcond(conflux_lu_ctx *ctx, double *rcond, double *anorm,
  * Logical order: the context remembers n.  conflux_lu_init_matrix*,
  * conflux_lu_set_matrix_local and the simulation upload reset it to
  * N_padded, after which everything behaves as it always did.  What follows
- * the logical order of the matrix last factored: the *_device calls below,
+ * the logical order of the matrix last factored: the *_device calls below
+ * (the refined solves conflux_lu_solve_refined_device /
+ * conflux_chol_solve_refined_device among them),
  * conflux_lu_slogdet / conflux_chol_logdet and conflux_lu_rcond /
  * conflux_chol_rcond.  What keeps describing the PADDED matrix:
  * conflux_lu_validate / conflux_chol_validate (the residual numerator is
@@ -350,6 +375,39 @@ int conflux_lu_solve_device(conflux_lu_ctx *ctx, double *dB, int64_t ldb,
 /* Same for the last Cholesky run (conflux_chol_solve's guards). */
 int conflux_chol_solve_device(conflux_lu_ctx *ctx, double *dB, int64_t ldb,
                               int nrhs, double *elapsed_ms);
+
+/* conflux_lu_solve_refined (trans = 0) / conflux_lu_solve_refined_trans
+ * (trans = 1) on the caller's device buffer: dB is n x nrhs, row-major,
+ * ldb >= nrhs, n the logical order of the matrix last factored; overwritten
+ * in place with X, the ldb - nrhs slack of every row is not touched.  The
+ * engine keeps its own zero-extended copy of B for the residual, so nothing
+ * but the window is written.  berr, ferr (host arrays of nrhs doubles),
+ * iters and elapsed_ms have conflux_lu_solve_refined's meaning and may be
+ * NULL.
+ * Everything describes the caller's n x n matrix: ||A|| in berr is the norm
+ * of the leading n x n block of the snapshot (inf-norm, 1-norm with trans —
+ * the figures conflux_lu_rcond reports), the residual and the column maxima
+ * range over the leading n rows, and the padding rows of X, R and D stay
+ * exactly zero.  With n == N_padded, X, berr, ferr and iters are bitwise
+ * those of the host entry points; max_iter = 0 gives X bitwise equal to
+ * conflux_lu_solve_device.
+ * CONFLUX_LU_EARG: dB == NULL, nrhs <= 0, ldb < nrhs, trans not 0/1,
+ * max_iter < 0, and every case in which conflux_lu_solve returns it
+ * (world > 1 included, before any communication). */
+int conflux_lu_solve_refined_device(conflux_lu_ctx *ctx, double *dB,
+                                    int64_t ldb, int nrhs, int trans,
+                                    int max_iter, double *berr, double *ferr,
+                                    int *iters, double *elapsed_ms);
+
+/* Same for the last Cholesky run (conflux_chol_solve_refined on a device
+ * buffer; max_iter = 0 is conflux_chol_solve_device bit for bit).  The
+ * both-triangles rule of conflux_chol_solve_refined still holds: the
+ * residual multiplies by the stored input as it stands, so the n x n matrix
+ * handed to conflux_lu_set_matrix_device must hold A in BOTH triangles. */
+int conflux_chol_solve_refined_device(conflux_lu_ctx *ctx, double *dB,
+                                      int64_t ldb, int nrhs, int max_iter,
+                                      double *berr, double *ferr, int *iters,
+                                      double *elapsed_ms);
 
 /* det(A) of the n x n matrix of the last store_factors LU run as
  * sign * exp(logabsdet): logabsdet = sum log|U_ii| over the leading n

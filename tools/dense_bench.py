@@ -3,7 +3,7 @@
 
     python tools/dense_bench.py [--N 16384] [--v 512] [--nrhs 1,16,128]
 
-Three tables, each figure the median of `--reps` wall-clock times around a
+Four tables, each figure the median of `--reps` wall-clock times around a
 call that returns with the engine's stream synchronized:
 
   import/export  the row-major import, the column-major import and the
@@ -14,6 +14,9 @@ call that returns with the engine's stream synchronized:
   solve          solve_device (B and X stay on the device) against the host
                  solve (B up and X down over PCIe) per nrhs: wall ms of the
                  whole call and the device ms of the two sweeps.
+  refined        solve_refined_device against the host refined solve on
+                 no-pivot factors, A X = B and A^T X = B, per nrhs: wall ms of
+                 the whole call and the device ms of the refinement loop.
   end to end     a device tensor A and B to a device tensor X:
                  device path = set_matrix_device + factor + solve_device;
                  host path   = A and B to the host, set_matrix_local (on one
@@ -120,6 +123,49 @@ def main():
                 N=N, v=v, nrhs=nrhs, dev_wall_ms=med(td), dev_sweeps_ms=med(sd),
                 host_wall_ms=med(th), host_sweeps_ms=med(sh),
                 dev_wall_all=td, host_wall_all=th, bitwise_equal=same)))
+
+        # refined solves: no-pivot factors, plain and transposed
+        e.set_pivoting(0)
+        e.set_matrix_device(pA, N, N, 0)
+        e.factor()
+        print(f"{'refined':>9} {'nrhs':>5} {'dev wall':>9} {'dev loop':>9} "
+              f"{'host wall':>9} {'host loop':>9} {'wall ratio':>10} "
+              f"{'iters':>5} {'berr':>9}")
+        for trans in (False, True):
+            hostfn = e.solve_transposed_refined if trans else e.solve_refined
+            name = "A^T X = B" if trans else "A X = B"
+            for nrhs in nrhs_list:
+                B = torch.randn((N, nrhs), dtype=torch.float64, device="cuda",
+                                generator=gen)
+                Bh = B.cpu().numpy()
+                X = B.clone()
+                e.solve_refined_device(X.data_ptr(), nrhs, nrhs, trans=trans)
+                hostfn(Bh)  # warm-up
+                td, sd, th, sh = [], [], [], []
+                for _ in range(a.reps):
+                    X.copy_(B)
+                    box = []
+                    td.append(wall_ms(lambda: box.append(
+                        e.solve_refined_device(X.data_ptr(), nrhs, nrhs,
+                                               trans=trans))))
+                    info = box[0]
+                    sd.append(info["ms"])
+                    box = []
+                    th.append(wall_ms(lambda: box.append(
+                        hostfn(Bh, return_info=True))))
+                    sh.append(box[0][1]["ms"])
+                same = bool(np.array_equal(X.cpu().numpy(), box[0][0]))
+                print(f"{name:>9} {nrhs:>5} {med(td):>9.3f} {med(sd):>9.3f} "
+                      f"{med(th):>9.3f} {med(sh):>9.3f} "
+                      f"{med(th) / med(td):>10.2f} {info['iters']:>5} "
+                      f"{info['berr'].max():>9.2e}")
+                print(json.dumps(dict(
+                    N=N, v=v, nrhs=nrhs, refined=True, trans=trans,
+                    dev_wall_ms=med(td), dev_loop_ms=med(sd),
+                    host_wall_ms=med(th), host_loop_ms=med(sh),
+                    dev_wall_all=td, host_wall_all=th, iters=info["iters"],
+                    berr=float(info["berr"].max()), bitwise_equal=same)))
+        e.set_pivoting(1)
 
         nrhs = nrhs_list[-1]
         B = torch.randn((N, nrhs), dtype=torch.float64, device="cuda",

@@ -15,6 +15,13 @@ evaluation R = B - A X, of one of its passes over A (a pass handles one
 column group) with the effective GB/s over N^2 * 8 B, next to a plain
 device-to-device copy of the same N^2 * 8 B in the same run.
 
+    python tools/solve_bench.py --refine --trans [--N 16384] [--v 512]
+
+--refine --trans does the same for conflux_lu_solve_refined_trans (plain
+column: conflux_lu_solve_trans), and its residual table times one transposed
+pass R = B - A^T X beside one plain pass R = B - A X and the device copy, all
+on one buffer in one run, with the ratio of the two passes.
+
     python tools/solve_bench.py --trans [--rcond] [--N 16384] [--v 512]
 
 --trans benchmarks conflux_lu_solve_trans next to the plain solve: per nrhs
@@ -51,6 +58,9 @@ def refine_main(a):
     nrhs_list = [int(x) for x in (a.nrhs or "1,16,128").split(",")]
     G = lib.conflux_lu_debug_residual_group_width()
     with conflux_amd.Engine(a.N, a.v, 1, 1, 1, rank=-1) as e:
+        plain = e.solve_transposed if a.trans else e.solve
+        refined = e.solve_transposed_refined if a.trans else e.solve_refined
+        what = "A^T X = B" if a.trans else "A X = B"
         N = e.Npad
         e.store_factors(True)
         e.init_matrix(42)
@@ -60,29 +70,32 @@ def refine_main(a):
             e.factor()  # warm-up
             fms = e.factor()
             name = "tournament" if piv else "no-pivot"
-            print(f"N={N} v={a.v} {name}: factor {fms:.1f} ms")
+            print(f"N={N} v={a.v} {name}, {what}: factor {fms:.1f} ms")
             print(f"{'nrhs':>5} {'plain ms':>9} {'refined ms':>10} {'iters':>5} "
                   f"{'berr plain':>11} {'berr refined':>12}")
             for nrhs in nrhs_list:
                 B = Bs[nrhs]
-                e.solve_refined(B)  # warm-up: code objects, allocator
+                refined(B)  # warm-up: code objects, allocator
                 tp, tr = [], []
                 for _ in range(a.reps):
-                    tp.append(e.solve(B, return_ms=True)[1])
-                    X, info = e.solve_refined(B, max_iter=a.max_iter,
-                                              return_info=True)
+                    tp.append(plain(B, return_ms=True)[1])
+                    X, info = refined(B, max_iter=a.max_iter,
+                                      return_info=True)
                     tr.append(info["ms"])
-                b0 = e.solve_refined(B, max_iter=0,
-                                     return_info=True)[1]["berr"].max()
+                b0 = refined(B, max_iter=0,
+                             return_info=True)[1]["berr"].max()
                 mp, mr = statistics.median(tp), statistics.median(tr)
                 print(f"{nrhs:>5} {mp:>9.3f} {mr:>10.3f} {info['iters']:>5} "
                       f"{b0:>11.2e} {info['berr'].max():>12.2e}")
                 print(json.dumps(dict(
                     N=N, v=a.v, nrhs=nrhs, pivoting=piv, factor_ms=fms,
+                    trans=bool(a.trans),
                     plain_ms_median=mp, refined_ms_median=mr,
                     refined_ms_all=tr, iters=info["iters"], berr_plain=b0,
                     berr_refined=float(info["berr"].max()),
                     ferr=float(info["ferr"].max()))))
+    if a.trans:
+        return residual_t_table(a, lib, N, nrhs_list, G)
     print(f"residual R = B - A X alone, {N} x {N}, column group {G}:")
     print(f"{'nrhs':>5} {'resid ms':>9} {'passes':>6} {'pass ms':>8} "
           f"{'GB/s':>8} {'copy ms':>8} {'copy GB/s (r+w)':>15}")
@@ -100,6 +113,38 @@ def refine_main(a):
         print(json.dumps(dict(N=N, nrhs=nrhs, resid_ms=ms_r.value,
                               passes=passes, pass_ms=pass_ms, pass_gbs=gbs,
                               copy_ms=ms_c.value, copy_gbs_rw=cgbs)))
+
+
+def residual_t_table(a, lib, N, nrhs_list, G):
+    import ctypes
+    C = lib.conflux_lu_debug_residual_t_chunk()
+    print(f"residual alone, {N} x {N}, column group {G}, transposed row "
+          f"chunk {C}: R = B - A^T X beside R = B - A X and the device copy")
+    print(f"{'nrhs':>5} {'passes':>6} {'T pass ms':>9} {'T GB/s':>8} "
+          f"{'pass ms':>8} {'GB/s':>8} {'T/plain':>7} {'copy ms':>8} "
+          f"{'copy GB/s (r+w)':>15}")
+    for nrhs in nrhs_list:
+        runs = []
+        for _ in range(a.reps):  # median of reps runs, each the mean of 4
+            o = [ctypes.c_double() for _ in range(3)]
+            rc = lib.conflux_lu_debug_residual_dd_t_bench(
+                N, N, nrhs, 4, *(ctypes.byref(x) for x in o))
+            assert rc == 0, rc
+            runs.append([x.value for x in o])
+        ms_t, ms_r, ms_c = (ctypes.c_double(statistics.median(r[i] for r in runs))
+                            for i in range(3))
+        passes = -(-nrhs // G)
+        pt, pp = ms_t.value / passes, ms_r.value / passes
+        gt = N * N * 8 / (pt * 1e-3) / 1e9
+        gp = N * N * 8 / (pp * 1e-3) / 1e9
+        cgbs = 2.0 * N * N * 8 / (ms_c.value * 1e-3) / 1e9
+        print(f"{nrhs:>5} {passes:>6} {pt:>9.3f} {gt:>8.1f} {pp:>8.3f} "
+              f"{gp:>8.1f} {pt / pp:>7.2f} {ms_c.value:>8.3f} {cgbs:>15.1f}")
+        print(json.dumps(dict(
+            N=N, nrhs=nrhs, passes=passes, resid_t_ms=ms_t.value,
+            resid_ms=ms_r.value, pass_t_ms=pt, pass_ms=pp, pass_t_gbs=gt,
+            pass_gbs=gp, t_over_plain=pt / pp, copy_ms=ms_c.value,
+            copy_gbs_rw=cgbs)))
 
 
 def trans_rcond_main(a):
